@@ -24,9 +24,19 @@ Steady-state semantics (any driver-chosen --steps window):
   the output) — nothing in the training step is skipped or cached.
 
 Launch (driver contract):
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+handed back to its caller as DIR/<name>.npy (float32): the next `states`,
+`reward`, `reach`, `collision`, `done`, plus `u_ref` on the captured path or
+`action` on the eager path, and `update_info` (float64: the metrics
+returned by the last update that ran inside the timed window, if any).
+Everything is seeded from --seed, so two runs with the same arguments start
+from identical scenes and weights and their dumps can be compared array by
+array.  --full is reserved for measurements beyond the headline figure;
+the headline is all this benchmark measures today.
 
 Weak scaling: each rank runs its own env replica; gradients all-reduce over
 RCCL/xGMI each inner iteration; whole-node value = N · K / max_rank_time.
@@ -56,6 +66,17 @@ def _barrier_sync(device):
         torch.distributed.barrier()
     if device.type == "cuda":
         torch.cuda.synchronize(device)
+
+
+def _dump_outputs(out_dir, arrays):
+    """Write each array as <out_dir>/<name>.npy (float32, or float64 where
+    it already is): the timed path's last-step outputs, a few KB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        if t.dtype != torch.float64:
+            t = t.float()
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.numpy())
 
 
 def _self_launch_torchrun(args):
@@ -133,7 +154,9 @@ def run(args):
     prob = 1 - (SCHEDULE_MIDPOINT - 1) / SCHEDULE_TOTAL
     updates = {"in_region": 0, "update_s": None, "step": 0}
 
-    def rollout_step(count=False):
+    def rollout_step(count=False, keep=None):
+        """One training env step.  `keep` (a dict) receives clones of what
+        this step hands back to its caller (--dump-outputs, last step)."""
         nonlocal data
         updates["step"] += 1
         take_explore = np.random.rand() < prob
@@ -142,7 +165,20 @@ def run(args):
         if engine is not None:
             # engine.step draws its own Bernoulli: pass prob 1/0 to pin the
             # branch we drew here (identical distribution, lets us count)
+            was_eager = engine._eager
             done = engine.step(prob=1.0 if take_explore else 0.0)
+            if keep is not None:
+                # before reload() overwrites the engine's state buffers
+                if was_eager:
+                    keep.update(states=env.data.states.clone())
+                else:
+                    c = engine.cur
+                    keep.update(states=engine.states[c].clone(),
+                                u_ref=engine.u_ref[c].clone(),
+                                reward=engine.reward_buf.clone(),
+                                reach=engine.reach_buf.clone(),
+                                collision=engine.coll_buf.clone())
+                keep["done"] = torch.tensor([float(done)])
             if done:
                 engine.reload()
                 if count:
@@ -151,10 +187,17 @@ def run(args):
             data.update(u_ref=env.u_ref(data))
             action = algo.step(data, prob=1.0 if take_explore else 0.0)
             next_data, reward, done, info = env.step(action)
+            if keep is not None:
+                keep.update(action=action.clone(),
+                            states=next_data.states.clone(),
+                            reward=reward.clone(),
+                            reach=info["reach"].clone(),
+                            collision=info["collision"].clone(),
+                            done=torch.tensor([float(done)]))
             data = env.reset() if done else next_data
 
     def run_update():
-        algo.update(updates["step"], None)
+        return algo.update(updates["step"], None)
 
     # ---- warmup (untimed, driver contract) ----
     for _ in range(args.warmup):
@@ -188,10 +231,13 @@ def run(args):
     # region after each full batch_size of steps, timed inline
     _barrier_sync(device)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        rollout_step(count=True)
+    last = {}           # outputs of the last timed step (--dump-outputs)
+    update_info = None  # return value of the last update inside the region
+    keep_at = args.steps - 1 if args.dump_outputs else -1
+    for i in range(args.steps):
+        rollout_step(count=True, keep=last if i == keep_at else None)
         if algo.buffer.size >= args.batch_size:
-            run_update()
+            update_info = run_update()
             updates["in_region"] += 1
     _barrier_sync(device)
     region = time.perf_counter() - t0
@@ -207,6 +253,13 @@ def run(args):
                          device=device if use_cuda else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        if update_info is not None:
+            last["update_info"] = torch.tensor(
+                [update_info[k] for k in sorted(update_info)],
+                dtype=torch.float64)
+        _dump_outputs(args.dump_outputs, last)
 
     if rank == 0:
         value = args.gpus * args.steps / elapsed
@@ -263,4 +316,15 @@ if __name__ == "__main__":
                    choices=[None, "bf16", "fp32"])
     p.add_argument("--no-capture", action="store_true", default=False,
                    help="disable the hipGraph rollout engine")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step returned (next states, rewards, reach / "
+                        "collision flags, done; the last in-window "
+                        "update's metrics if one ran) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true", default=False,
+                   help="also run the measurements beyond the headline "
+                        "figure; a plain run does only set-up, warm-up, "
+                        "the timed steps and the result line (today the "
+                        "headline is all this benchmark measures, so the "
+                        "two runs coincide)")
     run(p.parse_args())

@@ -81,6 +81,34 @@ def test_bench_contract():
     assert "ms_per_step" in j and "config" in j
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float .npy
+    files, identical from run to run under the same arguments; --full is
+    accepted and leaves the result line's contract intact."""
+    import numpy as np
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / name
+        r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7",
+                  "--warmup", "3", "--batch-size", "8", "-n", "4",
+                  "--dump-outputs", str(out)] + extra, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = json.loads(
+            [l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert j["steps"] == 7 and j["ms_per_step"] > 0
+        assert j["metric"] == "env-steps/sec (whole node)"
+        dumps.append({f.name: np.load(f) for f in sorted(out.iterdir())})
+    a, b = dumps
+    assert {"states.npy", "reward.npy", "reach.npy", "collision.npy",
+            "done.npy"} <= set(a)
+    assert set(a) == set(b)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.isfinite(a[name]).all(), name
+        assert np.array_equal(a[name], b[name]), name
+    assert a["states.npy"].shape == (4, 4)
+
+
 def test_bench_refuses_mislabeled_world():
     """Driver contract guard: WORLD_SIZE inconsistent with --gpus must
     exit non-zero instead of printing mislabeled numbers."""
