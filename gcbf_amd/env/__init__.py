@@ -11,15 +11,21 @@ from .dubins_car import DubinsCar
 
 def make_env(env: str, num_agents: int, device: torch.device, dt: float = 0.03,
              params: Optional[dict] = None,
-             max_neighbors: Optional[int] = None) -> MultiAgentEnv:
+             max_neighbors: Optional[int] = None,
+             device_reset: Optional[bool] = None) -> MultiAgentEnv:
+    """``device_reset``: sample episode resets on the device; ``None`` keeps
+    the env's default (off unless GCBF_AMD_DEVICE_RESET=1)."""
     if env == "SimpleCar":
-        return SimpleCar(num_agents, device, dt, params, max_neighbors)
+        e = SimpleCar(num_agents, device, dt, params, max_neighbors)
     elif env == "SimpleDrone":
-        return SimpleDrone(num_agents, device, dt, params, max_neighbors)
+        e = SimpleDrone(num_agents, device, dt, params, max_neighbors)
     elif env == "DubinsCar":
-        return DubinsCar(num_agents, device, dt, params, max_neighbors)
+        e = DubinsCar(num_agents, device, dt, params, max_neighbors)
     else:
         raise NotImplementedError("Env name not supported!")
+    if device_reset is not None:
+        e.set_device_reset(device_reset)
+    return e
 
 
 __all__ = ["MultiAgentEnv", "SimpleCar", "SimpleDrone", "DubinsCar",

@@ -7,6 +7,7 @@ gcbf/env/base.py:381-398.
 """
 from __future__ import annotations
 
+import os
 from abc import ABC, abstractmethod
 from typing import Optional, Tuple
 
@@ -33,6 +34,21 @@ class MultiAgentEnv(ABC):
         self._data: Optional[GraphBatch] = None
         self._t = 0
         self._mode = "train"
+        # opt-in device-side episode resets (ops.reset_sample); off keeps
+        # the host rejection loop and its CPU RNG stream untouched
+        self._device_reset = os.environ.get("GCBF_AMD_DEVICE_RESET") == "1"
+
+    @property
+    def device_reset(self) -> bool:
+        return self._device_reset
+
+    def set_device_reset(self, on: bool):
+        """Sample train/test resets on the device (True) or with the host
+        rejection loop (False).  Demo modes always use the host path."""
+        self._device_reset = bool(on)
+
+    def _use_device_reset(self) -> bool:
+        return self._device_reset and self._mode in ("train", "test")
 
     # mode switches (reference gcbf/env/base.py:33-40)
     def train(self):

@@ -34,7 +34,8 @@ from .. import ops
 from ..graph import GraphBatch
 from .demo_world import BoxWorld
 from .simple_car import SimpleCar
-from .utils import plot_graph, fig_to_rgb_array, rejection_sample_positions
+from .utils import plot_graph, fig_to_rgb_array, \
+    rejection_sample_positions, device_rejection_sample
 
 N_LIDAR_RAYS = 32  # reference gcbf/env/dubins_car.py:313
 
@@ -149,6 +150,8 @@ class DubinsCar(SimpleCar):
 
         if self._mode in ("demo_0", "demo_1", "demo_3"):
             return self._reset_demo()
+        if self._use_device_reset():
+            return self._reset_device()
 
         # obstacles: uniform positions, random heading/speed
         # (reference gcbf/env/dubins_car.py:392-401)
@@ -187,6 +190,38 @@ class DubinsCar(SimpleCar):
         self._data = self.add_communication_links(data)
 
         self._set_plot_limits(
+            torch.cat([states[:, :2], goals[:, :2], obs_pos], dim=0))
+        return self._data
+
+    def _reset_device(self) -> GraphBatch:
+        """train/test reset sampled on the device: obstacles drawn with the
+        device RNG, starts (4r) and goals (5r) as one B=2 launch of
+        ops.reset_sample with per-problem min_sep, both avoiding the
+        obstacle positions; no position is copied to the host."""
+        side = self._params["area_size"]
+        r = self._params["car_radius"]
+        obs_r = self._params["obs_point_r"]
+        n, dev = self.num_agents, self.device
+
+        obs = torch.rand(self._num_obs, self.state_dim, device=dev)
+        obs[:, :2] *= side
+        obs[:, 2] *= torch.pi * 2
+        obs[:, 3] *= self._params["obs_speed_limit"]
+        self._obs = obs
+        obs_pos = obs[:, :2].contiguous()
+
+        pos, goals2d = device_rejection_sample(
+            n, 2, side, (4 * r, 5 * r), obs_pos, 2 * r + 2 * obs_r, dev)
+
+        states = torch.cat([pos, torch.zeros(n, 2, device=dev)], dim=1)
+        states[:, 2] = torch.rand(n, device=dev) * 2 * torch.pi - torch.pi
+        goals = torch.cat([goals2d, torch.zeros(n, 2, device=dev)], dim=1)
+        goals[:, 2] = torch.rand(n, device=dev) * 2 * torch.pi - torch.pi
+        self._goal = goals
+
+        data = self._build_data(states)
+        self._data = self.add_communication_links(data)
+        self._finish_reset_plot_limits(
             torch.cat([states[:, :2], goals[:, :2], obs_pos], dim=0))
         return self._data
 
@@ -469,6 +504,7 @@ class DubinsCar(SimpleCar):
 
     @property
     def state_lim(self) -> Tuple[Tensor, Tensor]:
+        self._ensure_plot_limits()
         low = torch.tensor([self._xy_min[0], self._xy_min[1], -10, -10],
                            device=self.device)
         high = torch.tensor([self._xy_max[0], self._xy_max[1], 10, 10],
@@ -661,6 +697,7 @@ class DubinsCar(SimpleCar):
     def render(self, traj=None, return_ax: bool = False, plot_edge: bool = True,
                ax=None):
         import matplotlib.pyplot as plt
+        self._ensure_plot_limits()
         if self._mode in ("demo_0", "demo_1", "demo_3") and traj is None:
             return self._render_demo(plot_edge=plot_edge)
         return_tuple = True

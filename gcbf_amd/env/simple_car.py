@@ -17,7 +17,8 @@ from torch import Tensor
 from .. import ops
 from ..graph import GraphBatch
 from .base import MultiAgentEnv
-from .utils import lqr, plot_graph, fig_to_rgb_array, rejection_sample_positions
+from .utils import lqr, plot_graph, fig_to_rgb_array, \
+    rejection_sample_positions, device_rejection_sample
 
 
 class SimpleCar(MultiAgentEnv):
@@ -30,6 +31,8 @@ class SimpleCar(MultiAgentEnv):
         self._goal: Optional[Tensor] = None
         self._xy_min = None
         self._xy_max = None
+        # points whose plot limits are still owed (device-reset path)
+        self._plot_pts: Optional[Tensor] = None
 
     # ------------------------------------------------------------------ dims
     @property
@@ -85,7 +88,12 @@ class SimpleCar(MultiAgentEnv):
         self._t = 0
         side = self._params["area_size"]
         r = self._params["car_radius"]
-        if self._mode in ("train", "test", "demo_2"):
+        if self._use_device_reset():
+            # starts and goals as one B=2 launch (ops/hip/reset_sample.hip)
+            pos, goals = device_rejection_sample(
+                self.num_agents, 2, side, (4 * r, 4 * r), None, 0.0,
+                self.device)
+        elif self._mode in ("train", "test", "demo_2"):
             pos = rejection_sample_positions(self.num_agents, 2, side, 4 * r)
             if self._mode == "demo_2":
                 goals = self._sample_goals_near(pos, 4 * r)
@@ -104,7 +112,8 @@ class SimpleCar(MultiAgentEnv):
         data = self.add_communication_links(data)
         self._data = data
 
-        self._set_plot_limits(torch.cat([states[:, :2], goals], dim=0))
+        self._finish_reset_plot_limits(
+            torch.cat([states[:, :2], goals], dim=0))
         return data
 
     def _sample_goals_near(self, pos: Tensor, min_sep: float) -> Tensor:
@@ -124,7 +133,23 @@ class SimpleCar(MultiAgentEnv):
             i += 1
         return goals
 
+    def _finish_reset_plot_limits(self, points: Tensor):
+        """Host path: limits computed eagerly, as always.  Device path: the
+        points are kept on the device and the limits computed at the first
+        render (or state_lim) after the reset, so a reset copies no
+        positions back to the host."""
+        if self._use_device_reset():
+            self._plot_pts = points
+            self._xy_min = self._xy_max = None
+        else:
+            self._set_plot_limits(points)
+
+    def _ensure_plot_limits(self):
+        if self._plot_pts is not None:
+            self._set_plot_limits(self._plot_pts)
+
     def _set_plot_limits(self, points: Tensor):
+        self._plot_pts = None
         pts = points.detach().cpu().numpy()
         r = self._params["car_radius"]
         xy_min = np.min(pts, axis=0) - r * 5
@@ -249,6 +274,7 @@ class SimpleCar(MultiAgentEnv):
     # ---------------------------------------------------------------- limits
     @property
     def state_lim(self) -> Tuple[Tensor, Tensor]:
+        self._ensure_plot_limits()
         sl = self._params["speed_limit"]
         low = torch.tensor([self._xy_min[0], self._xy_min[1], -sl, -sl],
                            device=self.device)
@@ -365,6 +391,7 @@ class SimpleCar(MultiAgentEnv):
     def render(self, traj=None, return_ax: bool = False, plot_edge: bool = True,
                ax=None):
         import matplotlib.pyplot as plt
+        self._ensure_plot_limits()
         return_tuple = True
         if traj is None:
             traj = (self.data,)

@@ -22,7 +22,7 @@ from ..graph import GraphBatch
 from .base import MultiAgentEnv
 from .simple_car import SimpleCar
 from .utils import lqr, plot_graph_3d, fig_to_rgb_array, \
-    rejection_sample_positions
+    rejection_sample_positions, device_rejection_sample
 
 
 class SimpleDrone(MultiAgentEnv):
@@ -133,19 +133,31 @@ class SimpleDrone(MultiAgentEnv):
             raise NotImplementedError
 
         # reference quirk: always num_agents obstacles (simple_drone.py:128-135)
-        obs_pos = torch.rand(self.num_agents, 3) * side
-        self._obs = torch.zeros(self.num_agents, self.state_dim,
-                                device=self.device)
-        self._obs[:, :3] = obs_pos.to(self.device)
+        if self._use_device_reset():
+            # obstacles from the device RNG; starts and goals as one B=2
+            # launch (ops/hip/reset_sample.hip), nothing copied to the host
+            obs_pos = torch.rand(self.num_agents, 3, device=self.device) \
+                * side
+            self._obs = torch.zeros(self.num_agents, self.state_dim,
+                                    device=self.device)
+            self._obs[:, :3] = obs_pos
+            pos, goals3d = device_rejection_sample(
+                self.num_agents, 3, side, (4 * r, 4 * r), obs_pos,
+                2 * r + 2 * obs_r, self.device)
+        else:
+            obs_pos = torch.rand(self.num_agents, 3) * side
+            self._obs = torch.zeros(self.num_agents, self.state_dim,
+                                    device=self.device)
+            self._obs[:, :3] = obs_pos.to(self.device)
 
-        pos = rejection_sample_positions(
-            self.num_agents, 3, side, 4 * r,
-            avoid=obs_pos, avoid_dist=2 * r + 2 * obs_r)
-        goals3d = rejection_sample_positions(
-            self.num_agents, 3, side, 4 * r,
-            avoid=obs_pos, avoid_dist=2 * r + 2 * obs_r)
-        pos = pos.to(self.device)
-        goals3d = goals3d.to(self.device)
+            pos = rejection_sample_positions(
+                self.num_agents, 3, side, 4 * r,
+                avoid=obs_pos, avoid_dist=2 * r + 2 * obs_r)
+            goals3d = rejection_sample_positions(
+                self.num_agents, 3, side, 4 * r,
+                avoid=obs_pos, avoid_dist=2 * r + 2 * obs_r)
+            pos = pos.to(self.device)
+            goals3d = goals3d.to(self.device)
 
         states = torch.cat(
             [pos, torch.zeros(self.num_agents, 3, device=self.device)], dim=1)

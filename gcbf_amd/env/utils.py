@@ -135,6 +135,44 @@ def rejection_sample_positions(n: int, dim: int, side_length: float,
     return pts
 
 
+def device_rejection_sample(n: int, dim: int, side: float, min_seps,
+                            avoid: Optional[Tensor], avoid_dist: float,
+                            device: torch.device,
+                            generator: Optional[torch.Generator] = None
+                            ) -> Tensor:
+    """Device-side rejection sampling of ``B = len(min_seps)`` independent
+    sets of n points in [0, side)^dim, returned as (B, n, dim) on ``device``.
+
+    Same acceptance rule as :func:`rejection_sample_positions` (origin quirk
+    included), but the candidates are drawn as one pool per problem with
+    ``torch.rand(..., device=device)`` and scanned by ``ops.reset_sample``
+    (reset_sample.hip on GPU, the eager oracle on CPU); problem ``b`` uses
+    ``min_seps[b]``, all share ``avoid`` (A, dim) at ``avoid_dist``.  The
+    only host read-back is ``count``, once per pool.  The layouts come from
+    the device RNG, so they differ from the host path's for the same seed
+    (same distribution).
+
+    Unlike the host loop, which never returns on an infeasible layout, this
+    raises ``RuntimeError`` after 64 pools.
+    """
+    from .. import ops
+    B = len(min_seps)
+    C = 64 * ((2 * n + 64 + 63) // 64)
+    min_sep = torch.tensor([float(s) for s in min_seps], dtype=torch.float32,
+                           device=device)
+    pts = torch.zeros(B, n, dim, device=device)
+    count = torch.zeros(B, dtype=torch.int32, device=device)
+    for _ in range(64):
+        cand = torch.rand(B, C, dim, device=device, generator=generator) \
+            * side
+        ops.reset_sample(cand, min_sep, avoid, avoid_dist, pts, count)
+        if bool((count.cpu() >= n).all()):
+            return pts
+    raise RuntimeError(
+        f"device_rejection_sample: no valid layout for n={n} in "
+        f"[0, {side})^{dim} after 64 candidate pools")
+
+
 def create_point_cloud_surface(vertices: Tensor, r: float) -> Tensor:
     """Point cloud covering a quadrilateral surface (reference
     gcbf/env/utils.py:119-131)."""

@@ -283,3 +283,35 @@ def fused_masks(states: Tensor, batch: int, n_rec: int, radius: float,
     res = ext.fused_masks(states.contiguous(), batch, n_rec, float(radius),
                           env_kind, idx == 0, idx == 1, idx == 2)
     return res[idx]
+
+
+# --------------------------------------------------------------------------
+# episode reset
+# --------------------------------------------------------------------------
+
+def reset_sample(cand: Tensor, min_sep: Tensor, avoid: Optional[Tensor],
+                 avoid_dist: float, pts: Tensor, count: Tensor) -> Tensor:
+    """Greedy rejection sampling over a pre-drawn candidate stream, ``B``
+    independent problems per call (reset_sample.hip; semantics in
+    :func:`eager.reset_sample`).
+
+    ``cand`` (B, C, dim) fp32, ``min_sep`` (B,) fp32, ``avoid`` (B, A, dim)
+    or (A, dim) shared by all problems or None, ``pts`` (B, n, dim) and
+    ``count`` (B,) int32 updated in place (resumable).  Returns ``used``
+    (B,) int32, the number of candidates consumed from this pool.  GPU
+    tensors run the HIP kernel (one wavefront per problem), CPU tensors the
+    eager oracle.
+    """
+    B, _, dim = cand.shape
+    if avoid is None:
+        avoid = cand.new_zeros(B, 0, dim)
+    elif avoid.dim() == 2:
+        avoid = avoid.unsqueeze(0).expand(B, -1, -1)
+    if cand.is_cuda:
+        ext = _require_ext("reset_sample")
+        if ext is not None:
+            return ext.reset_sample(
+                cand.contiguous(), min_sep.contiguous(), avoid.contiguous(),
+                float(avoid_dist), pts, count)
+    used, _ = eager.reset_sample(cand, min_sep, avoid, avoid_dist, pts, count)
+    return used

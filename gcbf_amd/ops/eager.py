@@ -147,3 +147,77 @@ def pairwise_dist_masked(states: Tensor, agent_mask: Optional[Tensor],
     am = agent_mask.view(B, N)
     n_rec = int(am[0].sum().item())
     return dist[:, :n_rec, :] + eye[:n_rec] * diag_offset
+
+
+# --------------------------------------------------------------------------
+# episode-reset rejection sampling over a pre-drawn candidate stream
+# --------------------------------------------------------------------------
+
+def _sq_dist(points: Tensor, p: Tensor) -> Tensor:
+    """fp32 squared distances, accumulated x, y(, z) in order, no sqrt."""
+    diff = points - p
+    d2 = diff[:, 0] * diff[:, 0]
+    for k in range(1, diff.shape[1]):
+        d2 = d2 + diff[:, k] * diff[:, k]
+    return d2
+
+
+def reset_sample(cand: Tensor, min_sep: Tensor, avoid: Tensor,
+                 avoid_dist: float, pts: Tensor, count: Tensor):
+    """Greedy sequential rejection sampling, the oracle of reset_sample.hip.
+
+    For each of the ``B`` problems walk ``cand[b]`` (C, dim) in order while
+    ``count[b] < n`` and accept a candidate iff its squared fp32 distance to
+    the origin (reference quirk: the host loop tests against a zero-
+    initialised buffer) and to every accepted point exceeds ``min_sep[b]²``
+    and its squared distance to every ``avoid[b]`` point exceeds
+    ``avoid_dist²``.  ``pts`` (B, n, dim) and ``count`` (B,) int32 are
+    updated in place, so a short problem can be resumed with a fresh pool.
+
+    Returns ``(used, min_gap)``: ``used`` (B,) int32 is the number of
+    candidates consumed from this pool (``C`` when it ran out), ``min_gap``
+    the smallest relative gap ``|d2 - thr²| / thr²`` over every comparison
+    made — how far the closest decision was from flipping under a different
+    fp32 rounding of ``d2``.
+    """
+    dev = cand.device
+    B, C, dim = cand.shape
+    n = pts.shape[1]
+    cand_c = cand.detach().float().cpu()
+    avoid_c = avoid.detach().float().cpu()
+    sep_c = min_sep.detach().float().cpu()
+    pts_c = pts.detach().cpu().clone()
+    count_c = count.detach().cpu().clone()
+    used = torch.zeros(B, dtype=torch.int32)
+    av = torch.tensor(float(avoid_dist), dtype=torch.float32)
+    av2 = av * av
+    min_gap = float("inf")
+    for b in range(B):
+        sep2 = sep_c[b] * sep_c[b]
+        # occupied = origin + accepted points
+        occ = torch.zeros(n + 1, dim)
+        cnt = min(max(int(count_c[b]), 0), n)
+        occ[1:cnt + 1] = pts_c[b, :cnt]
+        c = 0
+        while cnt < n and c < C:
+            p = cand_c[b, c]
+            c += 1
+            d2 = _sq_dist(occ[:cnt + 1], p)
+            ok = bool((d2 > sep2).all())
+            if float(sep2) > 0:
+                min_gap = min(min_gap, float(((d2 - sep2).abs() / sep2).min()))
+            if avoid_c.shape[1]:
+                d2a = _sq_dist(avoid_c[b], p)
+                ok = ok and bool((d2a > av2).all())
+                if float(av2) > 0:
+                    min_gap = min(min_gap,
+                                  float(((d2a - av2).abs() / av2).min()))
+            if ok:
+                cnt += 1
+                occ[cnt] = p
+        pts_c[b, :cnt] = occ[1:cnt + 1]
+        count_c[b] = cnt
+        used[b] = c
+    pts.copy_(pts_c.to(dev))
+    count.copy_(count_c.to(dev))
+    return used.to(dev), min_gap

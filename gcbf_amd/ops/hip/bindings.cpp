@@ -62,6 +62,12 @@ extern "C" void launch_drone_step(const float* states, const float* goal,
                                   float r, float sl, float d2g,
                                   float act_lim, hipStream_t stream);
 
+extern "C" void launch_reset_sample(const float* cand, const float* min_sep,
+                                    const float* avoid, float avoid_dist,
+                                    float* pts, int* count, int* used, int B,
+                                    int C, int A, int n, int dim,
+                                    hipStream_t stream);
+
 namespace {
 
 #define CHECK_IN(x)                                                    \
@@ -354,6 +360,43 @@ std::vector<torch::Tensor> drone_step(
     return out;
 }
 
+torch::Tensor reset_sample(torch::Tensor cand, torch::Tensor min_sep,
+                           torch::Tensor avoid, double avoid_dist,
+                           torch::Tensor pts, torch::Tensor count) {
+    // greedy rejection sampling over a candidate pool, one wave per problem;
+    // pts/count are updated in place (resumable), returns used (B,) int32
+    CHECK_IN(cand); CHECK_IN(min_sep); CHECK_IN(avoid);
+    CHECK_IN(pts); CHECK_IN(count);
+    TORCH_CHECK(cand.scalar_type() == torch::kFloat32 &&
+                min_sep.scalar_type() == torch::kFloat32 &&
+                avoid.scalar_type() == torch::kFloat32 &&
+                pts.scalar_type() == torch::kFloat32,
+                "cand, min_sep, avoid, pts must be fp32");
+    TORCH_CHECK(count.scalar_type() == torch::kInt32, "count must be int32");
+    TORCH_CHECK(cand.dim() == 3 && avoid.dim() == 3 && pts.dim() == 3,
+                "cand (B,C,dim), avoid (B,A,dim), pts (B,n,dim) expected");
+    const int64_t B = cand.size(0), C = cand.size(1), dim = cand.size(2);
+    const int64_t A = avoid.size(1), n = pts.size(1);
+    TORCH_CHECK(dim == 2 || dim == 3, "dim must be 2 or 3");
+    TORCH_CHECK(avoid.size(0) == B && avoid.size(2) == dim &&
+                pts.size(0) == B && pts.size(2) == dim &&
+                min_sep.numel() == B && count.numel() == B,
+                "reset_sample: batch/dim mismatch");
+    // accepted points are kept in LDS: n*dim floats (48 KiB at the cap)
+    TORCH_CHECK(n >= 0 && n <= 4096, "reset_sample: n must be <= 4096 "
+                "(LDS budget), got ", n);
+    TORCH_CHECK(C < (1 << 30) && A < (1 << 30), "pool too large");
+    auto used = torch::zeros({B}, count.options());
+    if (B > 0)
+        launch_reset_sample(cand.data_ptr<float>(),
+                            min_sep.data_ptr<float>(),
+                            avoid.data_ptr<float>(), (float)avoid_dist,
+                            pts.data_ptr<float>(), count.data_ptr<int>(),
+                            used.data_ptr<int>(), (int)B, (int)C, (int)A,
+                            (int)n, (int)dim, current_stream());
+    return used;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -389,4 +432,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("out") = py::none());
     m.def("fused_linear", &fused_linear,
           "MFMA bf16 GEMM with fused bias + activation epilogue");
+    m.def("reset_sample", &reset_sample,
+          "greedy rejection sampling over a candidate pool (episode reset)",
+          py::arg("cand"), py::arg("min_sep"), py::arg("avoid"),
+          py::arg("avoid_dist"), py::arg("pts"), py::arg("count"));
 }

@@ -69,7 +69,8 @@ def test(args):
     if args.sense_radius is not None:
         params["comm_radius"] = args.sense_radius
     env = make_env(env_name, num_agents, device, params=params,
-                   max_neighbors=max_neighbors)
+                   max_neighbors=max_neighbors,
+                   device_reset=True if args.device_reset else None)
     if args.demo is None:
         env.test()
     else:
@@ -187,4 +188,7 @@ if __name__ == "__main__":
     parser.add_argument("--cpu", action="store_true", default=False)
     parser.add_argument("--dtype", type=str, default=None,
                         choices=[None, "bf16", "fp32"])
+    parser.add_argument("--device-reset", action="store_true", default=False,
+                        help="sample episode resets on the device (HIP "
+                             "rejection-sampling kernel; device RNG stream)")
     test(parser.parse_args())

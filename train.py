@@ -43,11 +43,15 @@ def train(args):
     if args.obs is not None:
         params["num_obs"] = args.obs
     max_neighbors = 12 if args.algo == "macbf" else None
+    # --device-reset forces the device path on; without it the envs keep
+    # their default (off unless GCBF_AMD_DEVICE_RESET=1)
+    device_reset = True if args.device_reset else None
     env = make_env(args.env, args.num_agents, device, params=params,
-                   max_neighbors=max_neighbors)
+                   max_neighbors=max_neighbors, device_reset=device_reset)
     env.train()
     env_test = make_env(args.env, args.num_agents, device, params=params,
-                        max_neighbors=max_neighbors)
+                        max_neighbors=max_neighbors,
+                        device_reset=device_reset)
     env_test.train()
 
     hyper = read_params(args.env, args.algo)
@@ -134,4 +138,7 @@ if __name__ == "__main__":
     parser.add_argument("--resume", type=str, default=None,
                         help="path of a previous run's log dir to resume")
     parser.add_argument("--eval-epi", type=int, default=3)
+    parser.add_argument("--device-reset", action="store_true", default=False,
+                        help="sample episode resets on the device (HIP "
+                             "rejection-sampling kernel; device RNG stream)")
     train(parser.parse_args())
