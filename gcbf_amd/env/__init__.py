@@ -4,6 +4,7 @@ import torch
 from typing import Optional
 
 from .base import MultiAgentEnv
+from .point_agent import PointAgentEnv
 from .simple_car import SimpleCar
 from .simple_drone import SimpleDrone
 from .dubins_car import DubinsCar
@@ -28,5 +29,5 @@ def make_env(env: str, num_agents: int, device: torch.device, dt: float = 0.03,
     return e
 
 
-__all__ = ["MultiAgentEnv", "SimpleCar", "SimpleDrone", "DubinsCar",
+__all__ = ["MultiAgentEnv", "PointAgentEnv", "SimpleCar", "SimpleDrone", "DubinsCar",
            "make_env"]

@@ -33,14 +33,33 @@ from torch import Tensor
 from .. import ops
 from ..graph import GraphBatch
 from .demo_world import BoxWorld
-from .simple_car import SimpleCar
+from .point_agent import PointAgentEnv
 from .utils import plot_graph, fig_to_rgb_array, \
     rejection_sample_positions, device_rejection_sample
 
 N_LIDAR_RAYS = 32  # reference gcbf/env/dubins_car.py:313
 
 
-class DubinsCar(SimpleCar):
+class DubinsCar(PointAgentEnv):
+
+    pos_dim = 2
+    _radius_key = "car_radius"
+    _step_kind = "dubins"
+    _env_kind = ops.ENV_DUBINS
+    # the fused graph builder computes the 5-dim dubins edge_attr in its
+    # fill pass
+    _attr_kind = ops.ATTR_DUBINS
+    _action_limit = 2.0
+    # reference gcbf/env/dubins_car.py:522-615; the action cost is one sum
+    # over all agents
+    _reward_step = -0.0001
+    _reward_collision = 0.1
+    _reward_reach = 10
+    _action_cost = 0.01
+    _action_cost_summed = True
+    # threshold 3r under a 4r+1 diagonal (reference dubins_car.py:835-838)
+    _safe_radii = 3
+    _warn_radii = 3
 
     def __init__(self, num_agents: int, device: torch.device, dt: float = 0.03,
                  params: Optional[dict] = None,
@@ -48,7 +67,6 @@ class DubinsCar(SimpleCar):
         super().__init__(num_agents, device, dt, params, max_neighbors)
         self._num_obs = self._params["num_obs"]
         self._params["obs_len_max"] = self._params["area_size"] / 8.0
-        self._obs: Optional[Tensor] = None  # obstacle states (n_obs, 4)
         # demo modes: native box world (analytic LiDAR + contacts — the
         # reference used pybullet here, gcbf/env/dubins_car.py:55-382)
         self._world: Optional[BoxWorld] = None
@@ -88,8 +106,16 @@ class DubinsCar(SimpleCar):
         return 4
 
     @property
+    def node_dim(self) -> int:
+        return 4
+
+    @property
     def edge_dim(self) -> int:
         return 5
+
+    @property
+    def action_dim(self) -> int:
+        return 2
 
     # -------------------------------------------------------------- dynamics
     def dynamics(self, data: GraphBatch, u) -> Tensor:
@@ -144,86 +170,60 @@ class DubinsCar(SimpleCar):
     # ----------------------------------------------------------------- reset
     def reset(self) -> GraphBatch:
         self._t = 0
-        side = self._params["area_size"]
-        r = self._params["car_radius"]
-        obs_r = self._params["obs_point_r"]
-
         if self._mode in ("demo_0", "demo_1", "demo_3"):
             return self._reset_demo()
-        if self._use_device_reset():
-            return self._reset_device()
+        draw = self._draw_device if self._use_device_reset() \
+            else self._draw_host
+        pos, goals2d = draw()
+        # headings from the env device's RNG, start before goal
+        states = self._at_rest(pos)
+        states[:, 2] = torch.rand(self.num_agents, device=self.device) \
+            * 2 * torch.pi - torch.pi
+        goals = self._at_rest(goals2d)
+        goals[:, 2] = torch.rand(self.num_agents, device=self.device) \
+            * 2 * torch.pi - torch.pi
+        return self._finish_reset(states, goals)
 
-        # obstacles: uniform positions, random heading/speed
-        # (reference gcbf/env/dubins_car.py:392-401)
+    def _draw_host(self) -> Tuple[Tensor, Tensor]:
+        """Obstacles, starts (4r) and goals (5r) from the CPU RNG with the
+        host rejection loop (reference gcbf/env/dubins_car.py:392-401)."""
+        side = self._params["area_size"]
+        r = self.agent_radius
+        clearance = 2 * r + 2 * self._params["obs_point_r"]
         obs_pos = torch.rand(self._num_obs, 2) * side
         obs = torch.rand(self._num_obs, self.state_dim)
         obs[:, :2] = obs_pos
         obs[:, 2] *= torch.pi * 2
         obs[:, 3] *= self._params["obs_speed_limit"]
         self._obs = obs.to(self.device)
-        obs_pos = obs_pos.to(self.device)
 
         pos = rejection_sample_positions(
             self.num_agents, 2, side, 4 * r,
-            avoid=obs_pos.cpu(), avoid_dist=2 * r + 2 * obs_r)
+            avoid=obs_pos, avoid_dist=clearance)
         if self._mode == "demo_2":
             goals2d = self._sample_goals_near(pos, 5 * r)
         else:
             goals2d = rejection_sample_positions(
                 self.num_agents, 2, side, 5 * r,
-                avoid=obs_pos.cpu(), avoid_dist=2 * r + 2 * obs_r)
-        pos = pos.to(self.device)
-        goals2d = goals2d.to(self.device)
+                avoid=obs_pos, avoid_dist=clearance)
+        return pos.to(self.device), goals2d.to(self.device)
 
-        states = torch.cat(
-            [pos, torch.zeros(self.num_agents, 2, device=self.device)], dim=1)
-        states[:, 2] = torch.rand(self.num_agents, device=self.device) \
-            * 2 * torch.pi - torch.pi
-        goals = torch.cat(
-            [goals2d, torch.zeros(self.num_agents, 2, device=self.device)],
-            dim=1)
-        goals[:, 2] = torch.rand(self.num_agents, device=self.device) \
-            * 2 * torch.pi - torch.pi
-        self._goal = goals
-
-        data = self._build_data(states)
-        self._data = self.add_communication_links(data)
-
-        self._set_plot_limits(
-            torch.cat([states[:, :2], goals[:, :2], obs_pos], dim=0))
-        return self._data
-
-    def _reset_device(self) -> GraphBatch:
-        """train/test reset sampled on the device: obstacles drawn with the
-        device RNG, starts (4r) and goals (5r) as one B=2 launch of
-        ops.reset_sample with per-problem min_sep, both avoiding the
-        obstacle positions; no position is copied to the host."""
+    def _draw_device(self) -> Tuple[Tensor, Tensor]:
+        """train/test draw on the device: obstacles from the device RNG,
+        starts (4r) and goals (5r) as one B=2 launch of ops.reset_sample
+        with per-problem min_sep, both avoiding the obstacle positions; no
+        position is copied to the host."""
         side = self._params["area_size"]
-        r = self._params["car_radius"]
-        obs_r = self._params["obs_point_r"]
-        n, dev = self.num_agents, self.device
-
-        obs = torch.rand(self._num_obs, self.state_dim, device=dev)
+        r = self.agent_radius
+        obs = torch.rand(self._num_obs, self.state_dim, device=self.device)
         obs[:, :2] *= side
         obs[:, 2] *= torch.pi * 2
         obs[:, 3] *= self._params["obs_speed_limit"]
         self._obs = obs
-        obs_pos = obs[:, :2].contiguous()
-
-        pos, goals2d = device_rejection_sample(
-            n, 2, side, (4 * r, 5 * r), obs_pos, 2 * r + 2 * obs_r, dev)
-
-        states = torch.cat([pos, torch.zeros(n, 2, device=dev)], dim=1)
-        states[:, 2] = torch.rand(n, device=dev) * 2 * torch.pi - torch.pi
-        goals = torch.cat([goals2d, torch.zeros(n, 2, device=dev)], dim=1)
-        goals[:, 2] = torch.rand(n, device=dev) * 2 * torch.pi - torch.pi
-        self._goal = goals
-
-        data = self._build_data(states)
-        self._data = self.add_communication_links(data)
-        self._finish_reset_plot_limits(
-            torch.cat([states[:, :2], goals[:, :2], obs_pos], dim=0))
-        return self._data
+        return device_rejection_sample(
+            self.num_agents, 2, side, (4 * r, 5 * r),
+            obs[:, :2].contiguous(),
+            2 * r + 2 * self._params["obs_point_r"], self.device)
 
     # ------------------------------------------------------- demo modes
     # Native replacements for the reference's pybullet demo paths
@@ -366,15 +366,9 @@ class DubinsCar(SimpleCar):
         if self._mode == "demo_3":  # reference shuffles goals (:311-312)
             goal_pos = goal_pos[torch.randperm(self.num_agents,
                                                device=self.device)]
-        self._goal = torch.cat(
-            [goal_pos, torch.zeros(self.num_agents, 2, device=self.device)],
-            dim=1)
-        obs_pos = self._lidar_observe(agent_pos)
-        data = self._build_data(states)
-        self._data = self.add_communication_links(data)
-        self._set_plot_limits(
-            torch.cat([states[:, :2], goal_pos, obs_pos], dim=0))
-        return self._data
+        self._goal = self._at_rest(goal_pos)  # the LiDAR sees the goals
+        self._lidar_observe(agent_pos)
+        return self._finish_reset(states, self._goal)
 
     def _step_demo(self, action: Tensor):
         """Demo-mode step (reference :525-615): integrate agents on the
@@ -387,105 +381,32 @@ class DubinsCar(SimpleCar):
         action = torch.clamp(action, lower_lim, upper_lim)
         am = self._data.agent_mask
         sel = am if am is not None else slice(None)
-        prev_reach = torch.less(
-            torch.norm(self.data.states[sel, :2] - self._goal[:, :2], dim=1),
-            self._params["dist2goal"])
+        prev_reach = self._reached(self._data.states[sel])
         with torch.no_grad():
             state = self.forward(self._data, action)
         agent_state = state[sel]
 
         if self._mode in ("demo_0", "demo_3"):
             self._world.advance(self.dt)
-            self._lidar_observe(agent_state[:, :2])
-        else:  # demo_1: no boxes; keep the (empty) point cloud
-            self._lidar_observe(agent_state[:, :2])
+        # demo_1 has no boxes and keeps the (empty) point cloud
+        self._lidar_observe(agent_state[:, :2])
         data = self._build_data(agent_state)
         self._data = self.add_communication_links(data)
 
-        time_up = self._t >= self.max_episode_steps
-        reach = torch.less(
-            torch.norm(agent_state[:, :2] - self._goal[:, :2], dim=1),
-            self._params["dist2goal"])
-        done = bool(time_up or reach.all())
+        reach = self._reached(agent_state)
         collision = self.collision_mask(self._data)
         reward = (reach.int() - prev_reach.int()).int() * 10 \
             - collision.int() * 0.1 - 0.0001 + reward_action
-        safe = 1.0 - collision.sum() / self.num_agents
-        return self.data, reward.detach(), done, {
-            "reach": reach, "collision": collision, "safe": safe}
-
-    def _build_data(self, agent_states: Tensor) -> GraphBatch:
-        n_obs = self._obs.shape[0]
-        x = torch.cat([
-            torch.zeros(self.num_agents, self.node_dim),
-            torch.ones(n_obs, self.node_dim)], dim=0).type_as(agent_states)
-        states = torch.cat([agent_states, self._obs], dim=0)
-        agent_mask = torch.zeros(self.num_agents + n_obs, dtype=torch.bool,
-                                 device=self.device)
-        agent_mask[:self.num_agents] = True
-        g = GraphBatch(x=x, pos=states[:, :2], states=states,
-                       agent_mask=agent_mask)
-        g.agents_first_n = self.num_agents
-        return g
+        return self._step_result(reward.detach(), reach, collision)
 
     # ------------------------------------------------------------------ step
+    def _get_K_tensor(self):
+        return None  # PID reference controller: the fused step takes no gain
+
     def step(self, action: Tensor) -> Tuple[GraphBatch, Tensor, bool, dict]:
         if self._mode in ("demo_0", "demo_1", "demo_3"):
             return self._step_demo(action)
-        self._t += 1
-        # fused single-kernel path on GPU (ops/hip/env_step.hip)
-        out = ops.env_step_fused(
-            "dubins", self._data.states, self._goal, action, self.dt,
-            self._params["car_radius"], self._params["speed_limit"],
-            self._params["dist2goal"], 2.0)
-        if out is not None:
-            return self._finish_fused_step(out)
-
-        # reference gcbf/env/dubins_car.py:522-615
-        reward_action = -torch.norm(action, dim=1).sum() * 0.01
-        action = action + self._step_u_ref()
-        lower_lim, upper_lim = self.action_lim
-        action = torch.clamp(action, lower_lim, upper_lim)
-        am = self._data.agent_mask
-        prev_reach = torch.less(
-            torch.norm(self.data.states[am, :2] - self._goal[:, :2], dim=1),
-            self._params["dist2goal"])
-        with torch.no_grad():
-            state = self.forward(self._data, action)
-
-        data = GraphBatch(
-            x=self._data.x, pos=state[:, :2], states=state, agent_mask=am)
-        data.agents_first_n = self.num_agents
-        self._obs = state[~am]
-        self._data = self.add_communication_links(data)
-
-        time_up = self._t >= self.max_episode_steps
-        reach = torch.less(
-            torch.norm(self.data.states[am, :2] - self._goal[:, :2], dim=1),
-            self._params["dist2goal"])
-        done = bool(time_up or reach.all())
-
-        collision = self.collision_mask(data)
-        reward_step = -0.0001
-        reward_collision = -collision.int() * 0.1
-        reward_reach = (reach.int() - prev_reach.int()).int() * 10
-        reward = reward_reach + reward_collision + reward_step + reward_action
-
-        safe = 1.0 - collision.sum() / self.num_agents
-        return self.data, reward.detach(), done, {
-            "reach": reach, "collision": collision, "safe": safe}
-
-    def forward_graph(self, data: GraphBatch, action: Tensor) -> GraphBatch:
-        # reference gcbf/env/dubins_car.py:617-635
-        action = action + self.u_ref(data)
-        lower_lim, upper_lim = self.action_lim
-        action = torch.clamp(action, lower_lim, upper_lim)
-        state = self.forward(data, action)
-        return data.replace(
-            edge_attr=self.edge_attr(state, data.edge_index),
-            pos=state[:, :2],
-            states=state,
-        )
+        return super().step(action)
 
     # ----------------------------------------------------------------- graph
     def edge_attr(self, state: Tensor, edge_index: Tensor) -> Tensor:
@@ -497,11 +418,6 @@ class DubinsCar(SimpleCar):
         return edge_info.index_select(0, edge_index[0]) - \
             edge_info.index_select(0, edge_index[1])
 
-    # dense builder with agent-only receivers comes from SimpleCar's
-    # add_communication_links; the fused GPU kernel computes the 5-dim
-    # dubins edge_attr in its fill pass
-    _attr_kind = ops.ATTR_DUBINS
-
     @property
     def state_lim(self) -> Tuple[Tensor, Tensor]:
         self._ensure_plot_limits()
@@ -511,22 +427,11 @@ class DubinsCar(SimpleCar):
                             device=self.device)
         return low, high
 
-    @property
-    def action_lim(self) -> Tuple[Tensor, Tensor]:
-        upper = torch.ones(2, device=self.device) * 2.0
-        return -upper, upper
-
     # ----------------------------------------------------------------- u_ref
     def u_ref(self, data: GraphBatch) -> Tensor:
         # PID heading/accel controller (reference gcbf/env/dubins_car.py:764-816)
-        am = data.agent_mask
-        if data.agent_index is not None:   # capture-safe integer indexing
-            states = data.states.index_select(0, data.agent_index)
-        elif am is not None:
-            states = data.states[am]
-        else:
-            states = data.states
-        states = states.reshape(-1, self.num_agents, self.state_dim)
+        states = self._agent_rows(data).reshape(
+            -1, self.num_agents, self.state_dim)
         diff = (states - self._goal).reshape(-1, self.state_dim)
         states = states.reshape(-1, self.state_dim)
 
@@ -559,82 +464,33 @@ class DubinsCar(SimpleCar):
         return torch.stack([omega, a], dim=-1).reshape(-1, self.action_dim)
 
     # ----------------------------------------------------------------- masks
-    def _pairwise_agent_rows(self, data: GraphBatch, diag_offset: float
-                             ) -> Tuple[Tensor, Tensor]:
-        """pos-diff (B, n_agents, N, 2) and distance with diag offset on the
-        agent-self entries."""
+    def _heading(self, agent_states: Tensor) -> Tensor:
+        theta = agent_states[..., 2]
+        return torch.stack([torch.cos(theta), torch.sin(theta)], dim=-1)
+
+    def collision_mask(self, data: GraphBatch) -> Tensor:
+        if self._mode not in ("demo_0", "demo_3"):
+            return super().collision_mask(data)
+        # agent-agent circles PLUS contact with the box obstacles
+        # (reference :900-920 used pybullet getClosestPoints over the
+        # env's CURRENT bodies for every graph in a batch — mirrored:
+        # the box term uses the env's current agent positions)
+        r = self.agent_radius
         B = data.num_graphs
         N = data.nodes_per_graph
         n = self.num_agents
-        sv = data.states.view(B, N, -1)
-        pd = sv[:, :n, :2].unsqueeze(2) - sv[:, :, :2].unsqueeze(1)
-        dist = pd.norm(dim=-1)
-        eye = torch.eye(N, device=data.device, dtype=dist.dtype)[:n]
-        return pd, dist + eye * diag_offset
-
-    _env_kind = ops.ENV_DUBINS
-
-    def safe_mask(self, data: GraphBatch, return_edge: bool = False) -> Tensor:
-        r = self._params["car_radius"]
-        if return_edge:
-            return data.edge_attr[:, :2].norm(dim=-1) > 4 * r
-        m = self._fused_mask(data, "safe")
-        if m is not None:
-            return m
-        # diag offset 4r+1, threshold 3r (reference dubins_car.py:835-838)
-        _, dist = self._pairwise_agent_rows(data, 4 * r + 1)
-        return (dist > 3 * r).min(dim=2)[0].reshape(-1).bool()
-
-    def unsafe_mask(self, data: GraphBatch, return_edge: bool = False) -> Tensor:
-        r = self._params["car_radius"]
-        if return_edge:
-            return data.edge_attr[:, :2].norm(dim=-1) < 2 * r
-        m = self._fused_mask(data, "unsafe")
-        if m is not None:
-            return m
-        pd, dist = self._pairwise_agent_rows(data, 4 * r + 1)
-        collision = (dist < 2 * r).max(dim=2)[0]
-
-        warn_zone = dist < 3 * r
-        pos_vec = -(pd / (pd.norm(dim=-1, keepdim=True) + 1e-4))
-        B, N = pd.shape[0], pd.shape[2]
-        n = self.num_agents
-        sv = data.states.view(B, N, -1)
-        theta = sv[:, :n, 2]
-        theta_vec = torch.stack([torch.cos(theta), torch.sin(theta)],
-                                dim=-1).unsqueeze(2)
-        inner = (pos_vec * theta_vec).sum(dim=-1)
-        thr = torch.cos(torch.asin(2 * r / (dist + 1e-7)))
-        unsafe = torch.logical_and(inner > thr, warn_zone).max(dim=2)[0]
-        return torch.logical_or(collision, unsafe).reshape(-1).bool()
-
-    def collision_mask(self, data: GraphBatch) -> Tensor:
-        r = self._params["car_radius"]
-        if self._mode in ("demo_0", "demo_3"):
-            # agent-agent circles PLUS contact with the box obstacles
-            # (reference :900-920 used pybullet getClosestPoints over the
-            # env's CURRENT bodies for every graph in a batch — mirrored:
-            # the box term uses the env's current agent positions)
-            B = data.num_graphs
-            N = data.nodes_per_graph
-            n = self.num_agents
-            sv = data.states.view(B, N, -1)[:, :n, :2]
-            pd = sv.unsqueeze(2) - sv.unsqueeze(1)
-            dist = pd.norm(dim=-1) + torch.eye(
-                n, device=data.device) * (2 * r + 1)
-            coll_agent = (dist < 2 * r).max(dim=2)[0].reshape(-1)
-            am = self._data.agent_mask
-            cur = self._data.states[am if am is not None else slice(None), :2]
-            coll_box = (self._world.min_distance(cur) - r <= 0) \
-                if self._world is not None and self._world.num_boxes \
-                else torch.zeros(n, dtype=torch.bool, device=data.device)
-            return torch.logical_or(
-                coll_agent, coll_box.repeat(B)).bool()
-        m = self._fused_mask(data, "collision")
-        if m is not None:
-            return m
-        _, dist = self._pairwise_agent_rows(data, 2 * r + 1)
-        return (dist < 2 * r).max(dim=2)[0].reshape(-1).bool()
+        sv = data.states.view(B, N, -1)[:, :n, :2]
+        pd = sv.unsqueeze(2) - sv.unsqueeze(1)
+        dist = pd.norm(dim=-1) + torch.eye(
+            n, device=data.device) * (2 * r + 1)
+        coll_agent = (dist < 2 * r).max(dim=2)[0].reshape(-1)
+        am = self._data.agent_mask
+        cur = self._data.states[am if am is not None else slice(None), :2]
+        coll_box = (self._world.min_distance(cur) - r <= 0) \
+            if self._world is not None and self._world.num_boxes \
+            else torch.zeros(n, dtype=torch.bool, device=data.device)
+        return torch.logical_or(
+            coll_agent, coll_box.repeat(B)).bool()
 
     # ---------------------------------------------------------------- render
     def _render_demo(self, plot_edge: bool = True):

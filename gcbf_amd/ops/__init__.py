@@ -236,12 +236,6 @@ def build_graph(pos: Tensor, states: Tensor, n_rec: Optional[int],
     return ei, eager_attr_fn(states, ei)
 
 
-def pairwise_dist_masked(states: Tensor, agent_mask: Optional[Tensor],
-                         batch: int, pos_dim: int, diag_offset: float) -> Tensor:
-    return eager.pairwise_dist_masked(states, agent_mask, batch, pos_dim,
-                                      diag_offset)
-
-
 def env_step_fused(kind: str, *args, out=None):
     """Fused single-graph rollout step (env_step.hip); None on CPU/no-ext.
 

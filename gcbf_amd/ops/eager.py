@@ -131,24 +131,6 @@ def dense_radius_graph(
     return torch.stack([src, dst], dim=0)
 
 
-def pairwise_dist_masked(states: Tensor, agent_mask: Optional[Tensor],
-                         batch: int, pos_dim: int,
-                         diag_offset: float) -> Tensor:
-    """(B, n_rec, N) pairwise position distances with ``diag_offset`` added on
-    the receiver-self diagonal — the shared core of the safe/unsafe/collision
-    masks (reference pattern at gcbf/env/simple_car.py:320-325)."""
-    B = batch
-    N = states.shape[0] // B
-    p = states.view(B, N, -1)[..., :pos_dim]
-    dist = (p.unsqueeze(2) - p.unsqueeze(1)).norm(dim=-1)
-    eye = torch.eye(N, device=states.device, dtype=dist.dtype)
-    if agent_mask is None:
-        return dist + eye * diag_offset
-    am = agent_mask.view(B, N)
-    n_rec = int(am[0].sum().item())
-    return dist[:, :n_rec, :] + eye[:n_rec] * diag_offset
-
-
 # --------------------------------------------------------------------------
 # episode-reset rejection sampling over a pre-drawn candidate stream
 # --------------------------------------------------------------------------

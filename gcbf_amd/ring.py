@@ -34,7 +34,7 @@ class RingStore:
         self.N = data.num_nodes
         self.n = env.num_agents
         self.S = env.state_dim
-        self.pd = 3 if env.state_dim == 6 else 2
+        self.pd = env.pos_dim
         self.ad = env.action_dim
         self.CAP = capacity
         dev = self.device

@@ -55,7 +55,7 @@ class RolloutEngine:
         self.algo = algo
         self.device = env.device
         self.n = env.num_agents
-        self.pos_dim = 3 if env.state_dim == 6 else 2
+        self.pos_dim = env.pos_dim
         self.edge_dim = env.edge_dim
 
         data = env.data if env.data is not None else env.reset()
@@ -72,10 +72,6 @@ class RolloutEngine:
 
         from gcbf_amd import _C
         self._ext = _C
-
-        kind_by_class = {"SimpleCar": "car", "DubinsCar": "dubins",
-                         "SimpleDrone": "drone"}
-        self.kind = kind_by_class[type(env).__name__]
 
         dev = self.device
         # ping-pong buffer PAIRS: each captured replay reads set i and the
@@ -105,8 +101,9 @@ class RolloutEngine:
         self.ecount_buf = torch.zeros(1, dtype=torch.int32, device=dev)
         self.E = 0
 
-        if self.kind in ("car", "drone"):
-            self.K = env._get_K_tensor().clone().contiguous()
+        # address-stable copy of the LQR gain (None: the env has none)
+        K = env._get_K_tensor()
+        self.K = None if K is None else K.clone().contiguous()
 
         self._load_graph_from_env()
         self._capture()
@@ -119,16 +116,6 @@ class RolloutEngine:
             algo._make_ring()
 
     # ----------------------------------------------------------------- body
-    def _step_args(self, action, i: int):
-        p = self.env.params
-        r_key = "drone_radius" if self.kind == "drone" else "car_radius"
-        act_lim = {"car": 10.0, "dubins": 2.0, "drone": 10.0}[self.kind]
-        base = [self.states[i], self.goal, action]
-        if self.kind in ("car", "drone"):
-            base.append(self.K)
-        return base + [self.env.dt, p[r_key], p["speed_limit"],
-                       p["dist2goal"], act_lim]
-
     def _body(self, explore: bool, i: int):
         o = 1 - i
         data = GraphBatch(x=self.x, pos=self.states[i][:, :self.pos_dim],
@@ -150,7 +137,8 @@ class RolloutEngine:
             # kernels write set o directly (out= buffers), so the replay
             # has no copy-back; ecount lands straight in flags[0]
             ops.env_step_fused(
-                self.kind, *self._step_args(action, i),
+                *self.env.fused_step_args(
+                    self.states[i], self.goal, action, self.K),
                 out=[self.states[o], self.u_ref[o], self.reward_buf,
                      self.reach_buf, self.coll_buf])
             self._ext.build_graph_padded(

@@ -77,7 +77,7 @@ class UpdateEngine:
         self.N = data.num_nodes            # nodes per graph (incl. obstacles)
         self.n = env.num_agents            # agent rows come first per graph
         self.S = env.state_dim
-        self.pd = 3 if env.state_dim == 6 else 2
+        self.pd = env.pos_dim
         self.nd = env.node_dim
         self.ad = env.action_dim
         self.ed = env.edge_dim

@@ -206,7 +206,6 @@ def test_gcbf_update_gpu_bf16():
 def test_fused_masks_match_eager(env_name, n, obs):
     """HIP fused mask kernel vs. the eager batched math on identical states
     (single graphs and batches)."""
-    import os
     from gcbf_amd.env import make_env
     from gcbf_amd.graph import GraphBatch
     from gcbf_amd.trainer.utils import set_seed
@@ -230,11 +229,7 @@ def test_fused_masks_match_eager(env_name, n, obs):
         for which, fn in [("safe", env.safe_mask), ("unsafe", env.unsafe_mask),
                           ("collision", env.collision_mask)]:
             got = fn(data)  # GPU -> fused kernel
-            os.environ["GCBF_AMD_FORCE_EAGER_MASKS"] = "1"
-            try:
-                ref = _eager_mask(env, data, which)
-            finally:
-                del os.environ["GCBF_AMD_FORCE_EAGER_MASKS"]
+            ref = _eager_mask(env, data, which)
             assert torch.equal(got.cpu(), ref.cpu()), \
                 f"{env_name} {which} mismatch"
 
