@@ -17,7 +17,9 @@ MI355X redesign points:
 from __future__ import annotations
 
 import os
-from typing import Callable, Optional
+import sys
+import time
+from typing import Callable, Optional, Union
 
 import numpy as np
 import torch
@@ -29,9 +31,118 @@ from ..controller import GNNController
 from ..env import MultiAgentEnv
 from ..graph import GraphBatch
 from ..nn import MLP, CBFGNNLayer
+from ..nn.fused import sync_bf16_mirrors
+from ..nn.mlp import sn_weight_reuse
 from ..utils.trace import trace_range
 from .base import Algorithm
 from .buffer import Buffer
+
+
+def _masked_mean(viol: Tensor, ok: Tensor, mask: Tensor,
+                 weight: Optional[Tensor]):
+    """Mean of ``viol`` (a loss) and of ``ok`` (an accuracy) over the rows
+    ``mask`` selects, as weighted sums: boolean-mask indexing (h[mask])
+    calls nonzero and forces a device→host sync per mask per inner
+    iteration; the weighted form is mathematically identical (incl. the
+    empty-mask fallbacks of loss 0 / acc 1) and stays on device."""
+    w = mask.to(viol.dtype)
+    if weight is not None:
+        w = w * weight
+    c = w.sum()
+    c1 = c.clamp(min=1)
+    any_ = (c > 0).to(viol.dtype)
+    loss = any_ * (viol * w).sum() / c1
+    acc = any_ * (ok.to(viol.dtype) * w).sum() / c1 + (1 - any_)
+    return loss, acc
+
+
+def _wmean(x: Tensor, w: Optional[Tensor], w_sum: Optional[Tensor]):
+    return torch.mean(x) if w is None else (x * w).sum() / w_sum
+
+
+def cbf_losses(h: Tensor, h_dot: Union[Tensor, Callable[[], Tensor]],
+               actions: Tensor, unsafe: Tensor, safe: Tensor, params: dict,
+               weight: Optional[Tensor] = None):
+    """The CBF-condition loss of every update path (reference
+    gcbf/algo/gcbf.py:167-215).  Returns ``(loss, log7)``; ``log7`` is the
+    detached stack loss unsafe, safe, h_dot, action; acc unsafe, safe, h_dot.
+
+    ``h`` [R, 1] and the ``unsafe``/``safe`` masks [R] share their rows
+    (agents for GCBF, edges for MACBF); ``actions`` is per agent.  ``h_dot``
+    is the caller's: GCBF adds the re-link residue, MACBF does not.  It may
+    be a zero-argument callable, evaluated after the mask terms: gradient
+    contributions accumulate into ``h`` in the reverse of the order their
+    consumers were created, and float addition does not associate, so the
+    eager paths keep the order they have always built the graph in.
+
+    ``weight=None`` takes plain means.  ``weight`` [R] (pad rows 0, for the
+    captured engine's fixed-capacity batch; needs per-row ``actions``)
+    multiplies the mask weights and turns the means into
+    ``(x * w).sum() / w.sum()``, exactly equal on the real rows.
+    """
+    eps, alpha = params["eps"], params["alpha"]
+    w_sum = None if weight is None else weight.sum()
+    hv = h[:, 0]
+    # unsafe region: h < 0; safe region: h > 0
+    loss_unsafe, acc_unsafe = _masked_mean(
+        torch.relu(hv + eps), hv < 0, unsafe, weight)
+    loss_safe, acc_safe = _masked_mean(
+        torch.relu(-hv + eps), hv >= 0, safe, weight)
+
+    if callable(h_dot):
+        h_dot = h_dot()
+    if weight is None:
+        hd, ha = h_dot, alpha * h
+    else:   # flat rows, to multiply by the per-row weight
+        hd, ha = h_dot[:, 0], hv * alpha
+    loss_h_dot = _wmean(torch.relu(-hd - ha + eps), weight, w_sum)
+    acc_h_dot = _wmean((hd + ha >= 0).to(hd.dtype), weight, w_sum)
+
+    loss_action = _wmean(torch.square(actions).sum(dim=1), weight, w_sum)
+
+    loss = (params["loss_unsafe_coef"] * loss_unsafe +
+            params["loss_safe_coef"] * loss_safe +
+            params["loss_h_dot_coef"] * loss_h_dot +
+            params["loss_action_coef"] * loss_action)
+    log7 = torch.stack([
+        loss_unsafe.detach(), loss_safe.detach(), loss_h_dot.detach(),
+        loss_action.detach(), acc_unsafe.detach(), acc_safe.detach(),
+        acc_h_dot.detach()])
+    return loss, log7
+
+
+class _UpdateProf:
+    """Wall-clock buckets of one ``update()``; every method is a no-op
+    unless GCBF_AMD_UPDATE_PROF=1."""
+
+    def __init__(self, device: torch.device):
+        self.on = os.environ.get("GCBF_AMD_UPDATE_PROF") == "1"
+        self.cuda = device.type == "cuda"
+        self.buckets = dict.fromkeys(("sample", "batch", "fwd", "mask",
+                                      "hdot", "bwd", "opt", "engine"), 0.0)
+        self.t0 = 0.0
+
+    def _now(self) -> float:
+        if self.cuda:
+            torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def start(self):
+        if self.on:
+            self.t0 = self._now()
+
+    def lap(self, name: str):
+        """Charge the time since the last start/lap to bucket ``name``."""
+        if self.on:
+            t1 = self._now()
+            self.buckets[name] += t1 - self.t0
+            self.t0 = t1
+
+    def report(self):
+        if self.on:
+            print("# update prof: " + " ".join(
+                f"{k}={v * 1000:.1f}ms" for k, v in self.buckets.items()),
+                file=sys.stderr, flush=True)
 
 
 class _Seq(nn.Module):
@@ -207,23 +318,50 @@ class GCBF(Algorithm):
             warnings.warn(f"update capture unavailable ({e}); eager updates")
             self._upd_engine = None
 
+    def _sample_batch(self, seg_len: int = 3) -> list:
+        """Segments from the current buffer and the replay memory, balanced
+        between safe and unsafe steps once there is a memory."""
+        if self.memory.size == 0:
+            graph_list = self.buffer.sample(self.batch_size // 5, seg_len)
+        else:
+            curr = self.buffer.sample(self.batch_size // 10, seg_len, True)
+            prev = self.memory.sample(
+                self.batch_size // 5 - self.batch_size // 10, seg_len, True)
+            graph_list = curr + prev
+        if not graph_list:
+            # degenerate batch_size (< 10): the reference's balanced
+            # quotas (n//2 draws) collapse to zero and it crashes at
+            # Batch.from_data_list([]); sample unbalanced instead
+            graph_list = self.buffer.sample(
+                max(1, self.batch_size // 5), seg_len)
+        return graph_list
+
+    def _zero_grad(self):
+        self.optim_cbf.zero_grad(set_to_none=True)
+        self.optim_actor.zero_grad(set_to_none=True)
+
+    def _optimizer_step(self):
+        """Everything between backward and the next forward: DP gradient
+        all-reduce, clipping, both Adam steps, bf16 mirror refresh."""
+        if self.grad_sync is not None:
+            with trace_range("gcbf/grad_allreduce"):
+                self.grad_sync()
+        with trace_range("gcbf/optim"):
+            torch.nn.utils.clip_grad_norm_(self.cbf.parameters(), 1e-3)
+            torch.nn.utils.clip_grad_norm_(self.actor.parameters(), 1e-3)
+            self.optim_cbf.step()
+            self.optim_actor.step()
+            # bf16 mirror refresh must follow EVERY step: fused Adam does
+            # not bump version counters, so lazy staleness checks miss it,
+            # and captured graphs (rollout and the update engine's) read
+            # the mirrors by address
+            sync_bf16_mirrors(self.cbf)
+            sync_bf16_mirrors(self.actor)
+
     def update(self, step: int, writer=None) -> dict:
-        seg_len = 3
         inner_iter = self.params["inner_iter"]
         logs = []  # deferred scalars, synced once at the end
-
-        prof = None
-        if os.environ.get("GCBF_AMD_UPDATE_PROF") == "1":
-            import time as _time
-            prof = {"sample": 0.0, "batch": 0.0, "fwd": 0.0, "mask": 0.0,
-                    "hdot": 0.0, "bwd": 0.0, "opt": 0.0, "engine": 0.0}
-
-            def _tick():
-                if self.device.type == "cuda":
-                    torch.cuda.synchronize()
-                return _time.perf_counter()
-        else:
-            _tick = None
+        prof = _UpdateProf(self.device)
 
         if self._ring is None and not self._ring_tried:
             self._make_ring()
@@ -231,53 +369,27 @@ class GCBF(Algorithm):
             self._make_update_engine()
 
         for i_inner in range(inner_iter):
-            t0 = _tick() if prof else 0
-            # sample segments from the current buffer and the replay memory
-            if self.memory.size == 0:
-                graph_list = self.buffer.sample(self.batch_size // 5, seg_len)
-            else:
-                curr = self.buffer.sample(self.batch_size // 10, seg_len, True)
-                prev = self.memory.sample(
-                    self.batch_size // 5 - self.batch_size // 10, seg_len, True)
-                graph_list = curr + prev
-            if not graph_list:
-                # degenerate batch_size (< 10): the reference's balanced
-                # quotas (n//2 draws) collapse to zero and it crashes at
-                # Batch.from_data_list([]); sample unbalanced instead
-                graph_list = self.buffer.sample(
-                    max(1, self.batch_size // 5), seg_len)
-            if prof:
-                t1 = _tick(); prof["sample"] += t1 - t0; t0 = t1
+            prof.start()
+            graph_list = self._sample_batch()
+            prof.lap("sample")
 
             log7 = None
             if self._upd_engine is not None:
                 log7 = self._upd_engine.try_iter(graph_list)
-                if prof and log7 is not None:
-                    t1 = _tick(); prof["engine"] += t1 - t0; t0 = t1
+                if log7 is not None:
+                    prof.lap("engine")
             if log7 is None:
-                try:
-                    log7 = self._iter_eager(graph_list, prof, _tick)
-                except Exception:
-                    if getattr(self, "_sn_ctx", None) is not None:
-                        self._sn_ctx.__exit__()
-                        self._sn_ctx = None
-                    raise
+                log7 = self._iter_eager(graph_list, prof)
             logs.append(log7)
 
-        if prof:
-            import sys
-            print("# update prof: " + " ".join(
-                f"{k}={v * 1000:.1f}ms" for k, v in prof.items()),
-                file=sys.stderr, flush=True)
-
+        prof.report()
         return self._update_tail(step, writer, logs, inner_iter)
 
-    def _iter_eager(self, graph_list, prof=None, _tick=None) -> Tensor:
+    def _iter_eager(self, graph_list, prof=None) -> Tensor:
         """One eager inner iteration (sampled batch -> losses -> backward ->
         optimizer).  Returns the 7-scalar log stack (device tensor)."""
-        eps = self.params["eps"]
-        alpha = self.params["alpha"]
-        t0 = _tick() if prof else 0
+        prof = prof or _UpdateProf(self.device)
+        prof.start()
 
         graphs = None
         if self._ring is not None and self._ring.usable(graph_list):
@@ -295,108 +407,52 @@ class GCBF(Algorithm):
         if graphs is None:
             graphs = GraphBatch.from_list(graph_list)
         graphs.edge_attr.requires_grad_(True)
-        if prof:
-            t1 = _tick(); prof["batch"] += t1 - t0; t0 = t1
-        from ..nn.mlp import sn_weight_reuse
-        self._sn_ctx = sn_weight_reuse().__enter__()
-        with trace_range("gcbf/forward"):
-            actions = self.actor(graphs)
-            # h and h_next in ONE doubled-batch CBF forward: halves the
-            # CBF forward/backward chains vs. the reference's separate
-            # calls (gcbf/algo/gcbf.py:161,194) and evaluates both sides
-            # of the finite difference under the SAME spectral-norm σ
-            graphs_next = self._env.forward_graph(graphs, actions)
-            both = GraphBatch.from_list([graphs, graphs_next])
-            h_both = self.cbf(both)
-            n_ag = h_both.shape[0] // 2
-            h, h_next = h_both[:n_ag], h_both[n_ag:]
-        if prof:
-            t1 = _tick(); prof["fwd"] += t1 - t0; t0 = t1
+        prof.lap("batch")
+        # σ reuse ends before backward: the optimizer step changes the weights
+        with sn_weight_reuse():
+            with trace_range("gcbf/forward"):
+                actions = self.actor(graphs)
+                # h and h_next in ONE doubled-batch CBF forward: halves the
+                # CBF forward/backward chains vs. the reference's separate
+                # calls (gcbf/algo/gcbf.py:161,194) and evaluates both sides
+                # of the finite difference under the SAME spectral-norm σ
+                graphs_next = self._env.forward_graph(graphs, actions)
+                both = GraphBatch.from_list([graphs, graphs_next])
+                h_both = self.cbf(both)
+                n_ag = h_both.shape[0] // 2
+                h, h_next = h_both[:n_ag], h_both[n_ag:]
+            prof.lap("fwd")
 
-        # unsafe region: h < 0 (reference gcbf/algo/gcbf.py:167-177).
-        # Masked means are computed as weighted sums: boolean-mask
-        # indexing (h[mask]) calls nonzero and forces a device→host
-        # sync per mask per inner iteration; the weighted form is
-        # mathematically identical (incl. the empty-mask fallbacks of
-        # loss 0 / acc 1) and stays on device.
-        unsafe_mask = self._env.unsafe_mask(graphs)
-        hv = h[:, 0]
-        wu = unsafe_mask.to(hv.dtype)
-        cu = wu.sum()
-        cu1 = cu.clamp(min=1)
-        any_u = (cu > 0).to(hv.dtype)
-        loss_unsafe = any_u * (torch.relu(hv + eps) * wu).sum() / cu1
-        acc_unsafe = (any_u * ((hv < 0).to(hv.dtype) * wu).sum() / cu1
-                      + (1 - any_u))
+            unsafe_mask = self._env.unsafe_mask(graphs)
+            safe_mask = self._env.safe_mask(graphs)
+            prof.lap("mask")
 
-        # safe region: h > 0
-        safe_mask = self._env.safe_mask(graphs)
-        ws = safe_mask.to(hv.dtype)
-        cs = ws.sum()
-        cs1 = cs.clamp(min=1)
-        any_s = (cs > 0).to(hv.dtype)
-        loss_safe = any_s * (torch.relu(-hv + eps) * ws).sum() / cs1
-        acc_safe = (any_s * ((hv >= 0).to(hv.dtype) * ws).sum() / cs1
-                    + (1 - any_s))
+            # ḣ condition with the re-link residue trick
+            # (reference gcbf/algo/gcbf.py:191-209): the VALUE reflects the
+            # re-linked next graph, the GRADIENT flows through the
+            # fixed-topology path.
+            with trace_range("gcbf/h_dot"):
+                with torch.no_grad():
+                    relinked = self._env.add_communication_links_batched(
+                        graphs_next.detach())
+                    h_next_new_link = self.cbf(relinked)
+        prof.lap("hdot")
 
-        if prof:
-            t1 = _tick(); prof["mask"] += t1 - t0; t0 = t1
-        # ḣ condition with the re-link residue trick
-        # (reference gcbf/algo/gcbf.py:191-209): the VALUE reflects the
-        # re-linked next graph, the GRADIENT flows through the
-        # fixed-topology path.
-        with trace_range("gcbf/h_dot"):
-            with torch.no_grad():
-                relinked = self._env.add_communication_links_batched(
-                    graphs_next.detach())
-                h_next_new_link = self.cbf(relinked)
-        # σ reuse stops here: the optimizer step below changes the weights
-        self._sn_ctx.__exit__()
-        self._sn_ctx = None
-        h_dot = (h_next - h) / self._env.dt
-        h_dot_new_link = (h_next_new_link - h) / self._env.dt
-        residue = (h_dot_new_link - h_dot).detach()
-        h_dot = residue + h_dot
+        def h_dot():
+            h_dot = (h_next - h) / self._env.dt
+            h_dot_new_link = (h_next_new_link - h) / self._env.dt
+            residue = (h_dot_new_link - h_dot).detach()
+            return residue + h_dot
 
-        if prof:
-            t1 = _tick(); prof["hdot"] += t1 - t0; t0 = t1
-        loss_h_dot = torch.mean(torch.relu(-h_dot - alpha * h + eps))
-        acc_h_dot = torch.mean(
-            torch.greater_equal(h_dot + alpha * h, 0).type_as(h_dot))
-
-        loss_action = torch.mean(torch.square(actions).sum(dim=1))
-
-        loss = (self.params["loss_unsafe_coef"] * loss_unsafe +
-                self.params["loss_safe_coef"] * loss_safe +
-                self.params["loss_h_dot_coef"] * loss_h_dot +
-                self.params["loss_action_coef"] * loss_action)
-
-        self.optim_cbf.zero_grad(set_to_none=True)
-        self.optim_actor.zero_grad(set_to_none=True)
+        loss, log7 = cbf_losses(h, h_dot, actions, unsafe_mask, safe_mask,
+                                self.params)
+        self._zero_grad()
         with trace_range("gcbf/backward"):
             loss.backward()
-        if self.grad_sync is not None:
-            with trace_range("gcbf/grad_allreduce"):
-                self.grad_sync()
-        if prof:
-            t1 = _tick(); prof["bwd"] += t1 - t0; t0 = t1
-        with trace_range("gcbf/optim"):
-            torch.nn.utils.clip_grad_norm_(self.cbf.parameters(), 1e-3)
-            torch.nn.utils.clip_grad_norm_(self.actor.parameters(), 1e-3)
-            self.optim_cbf.step()
-            self.optim_actor.step()
-            # bf16 mirror refresh must follow EVERY step: fused Adam does
-            # not bump version counters, so lazy staleness checks miss it
-            from ..nn.fused import sync_bf16_mirrors
-            sync_bf16_mirrors(self.cbf)
-            sync_bf16_mirrors(self.actor)
-
-        if prof:
-            t1 = _tick(); prof["opt"] += t1 - t0
-        return torch.stack([
-            loss_unsafe.detach(), loss_safe.detach(),
-            loss_h_dot.detach(), loss_action.detach(),
-            acc_unsafe.detach(), acc_safe.detach(), acc_h_dot.detach()])
+        prof.lap("bwd")
+        self._optimizer_step()
+        prof.lap("opt")
+        return log7
 
     def _update_tail(self, step, writer, logs, inner_iter) -> dict:
         # one host sync for the whole update's scalars; under DP the stack
@@ -419,7 +475,6 @@ class GCBF(Algorithm):
 
         # refresh bf16 weight mirrors (captured rollout graphs read them
         # by address; Python is skipped during replay)
-        from ..nn.fused import sync_bf16_mirrors
         sync_bf16_mirrors(self.actor)
         sync_bf16_mirrors(self.cbf)
 

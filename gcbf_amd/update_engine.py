@@ -59,6 +59,7 @@ from __future__ import annotations
 
 import torch
 
+from .algo.gcbf import cbf_losses
 from .graph import GraphBatch
 
 
@@ -193,8 +194,6 @@ class UpdateEngine:
         (hand-capturing the backward measured corrupted bias gradients —
         grad buffers aliased freed forward temporaries in the shared pool)."""
         algo, env = self.algo, self.env
-        p = algo.params
-        eps, alpha = p["eps"], p["alpha"]
 
         gcur = GraphBatch(x=self.x_tile, pos=nodes[:, :self.pd],
                           states=nodes, edge_index=ei, edge_attr=ea,
@@ -224,52 +223,19 @@ class UpdateEngine:
         both.agent_index = self.agent_index2
         h_both = algo.cbf(both)
         h, h_next = h_both[:self.nA], h_both[self.nA:]
-        hv = h[:, 0]
-
-        # per-AGENT-row weights (h/actions/masks are per agent)
+        # per-AGENT-row weights (h/actions/masks are per agent); the pad
+        # rows carry weight 0
         w_node = w_dev.view(self.G_cap, 1).expand(
             self.G_cap, self.n).reshape(self.nA)
-        cw = w_node.sum()
 
-        # identical weighted-sum forms as GCBF._iter_eager, with the pad
-        # rows carrying weight 0
-        wu = env.unsafe_mask(gcur).to(hv.dtype) * w_node
-        cu = wu.sum()
-        cu1 = cu.clamp(min=1)
-        any_u = (cu > 0).to(hv.dtype)
-        loss_unsafe = any_u * (torch.relu(hv + eps) * wu).sum() / cu1
-        acc_unsafe = (any_u * ((hv < 0).to(hv.dtype) * wu).sum() / cu1
-                      + (1 - any_u))
+        def h_dot():
+            h_dot = (h_next - h) / env.dt
+            h_dot_new_link = (h_new - h) / env.dt
+            residue = (h_dot_new_link - h_dot).detach()
+            return residue + h_dot
 
-        ws = env.safe_mask(gcur).to(hv.dtype) * w_node
-        cs = ws.sum()
-        cs1 = cs.clamp(min=1)
-        any_s = (cs > 0).to(hv.dtype)
-        loss_safe = any_s * (torch.relu(-hv + eps) * ws).sum() / cs1
-        acc_safe = (any_s * ((hv >= 0).to(hv.dtype) * ws).sum() / cs1
-                    + (1 - any_s))
-
-        h_dot = (h_next - h) / env.dt
-        h_dot_new_link = (h_new - h) / env.dt
-        residue = (h_dot_new_link - h_dot).detach()
-        h_dot = residue + h_dot
-        hd = h_dot[:, 0]
-        ha = hv * alpha
-        loss_h_dot = (torch.relu(-hd - ha + eps) * w_node).sum() / cw
-        acc_h_dot = (((hd + ha) >= 0).to(hv.dtype) * w_node).sum() / cw
-
-        loss_action = (torch.square(actions).sum(dim=1) * w_node).sum() / cw
-
-        loss = (p["loss_unsafe_coef"] * loss_unsafe +
-                p["loss_safe_coef"] * loss_safe +
-                p["loss_h_dot_coef"] * loss_h_dot +
-                p["loss_action_coef"] * loss_action)
-
-        log7 = torch.stack([
-            loss_unsafe.detach(), loss_safe.detach(), loss_h_dot.detach(),
-            loss_action.detach(), acc_unsafe.detach(), acc_safe.detach(),
-            acc_h_dot.detach()])
-        return loss, log7
+        return cbf_losses(h, h_dot, actions, env.unsafe_mask(gcur),
+                          env.safe_mask(gcur), algo.params, weight=w_node)
 
     # ------------------------------------------------------------ capture
     def _fill_inputs(self, graph_list):
@@ -283,34 +249,6 @@ class UpdateEngine:
         self.w_host[L:] = 0.0
         self.idx_dev.copy_(self.idx_host, non_blocking=True)
         self.w_dev.copy_(self.w_host, non_blocking=True)
-
-    def _sample_for_warmup(self):
-        algo = self.algo
-        seg_len = 3
-        if algo.memory.size == 0:
-            return algo.buffer.sample(algo.batch_size // 5, seg_len)
-        curr = algo.buffer.sample(algo.batch_size // 10, seg_len, True)
-        prev = algo.memory.sample(
-            algo.batch_size // 5 - algo.batch_size // 10, seg_len, True)
-        return curr + prev
-
-    def _opt_tail(self):
-        algo = self.algo
-        if algo.grad_sync is not None:
-            algo.grad_sync()
-        torch.nn.utils.clip_grad_norm_(algo.cbf.parameters(), 1e-3)
-        torch.nn.utils.clip_grad_norm_(algo.actor.parameters(), 1e-3)
-        algo.optim_cbf.step()
-        algo.optim_actor.step()
-        # captured graphs (rollout AND this engine's) read the bf16
-        # mirrors by address — refresh after every weight change
-        from .nn.fused import sync_bf16_mirrors
-        sync_bf16_mirrors(algo.actor)
-        sync_bf16_mirrors(algo.cbf)
-
-    def _zero_grads(self):
-        self.algo.optim_cbf.zero_grad(set_to_none=True)
-        self.algo.optim_actor.zero_grad(set_to_none=True)
 
     def _build(self):
         algo = self.algo
@@ -346,17 +284,17 @@ class UpdateEngine:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(self.WARMUP_ITERS):
-                self._fill_inputs(self._sample_for_warmup())
+                self._fill_inputs(self.algo._sample_batch())
                 front = self._front()
                 if int(front[6].max().cpu()) > self.E_cap:
                     raise RuntimeError("edge overflow during warmup")
                 loss, _ = self._back_mod(*front[:6], self.w_dev)
-                self._zero_grads()
+                self.algo._zero_grad()
                 loss.backward()
-                self._opt_tail()
+                self.algo._optimizer_step()
         torch.cuda.current_stream().wait_stream(s)
 
-        self._fill_inputs(self._sample_for_warmup())
+        self._fill_inputs(self.algo._sample_batch())
         self.gFront = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.gFront):
             (self._nodes, self._uref, self._ei, self._ea, self._seg,
@@ -390,9 +328,9 @@ class UpdateEngine:
         loss, log7 = self._graphed(self._nodes, self._uref, self._ei,
                                    self._ea, self._seg, self._h_new,
                                    self.w_dev)
-        self._zero_grads()
+        self.algo._zero_grad()
         loss.backward()
-        self._opt_tail()
+        self.algo._optimizer_step()
         return log7.clone()
 
 

@@ -300,3 +300,106 @@ def test_ring_eviction_falls_back_to_from_list():
     assert all(np.isfinite(v) for v in out.values())
     # appends must have rotated past the ring window (fallback exercised)
     assert algo._ring.next_id > 30
+
+
+# ---------------------------------------------------------------- cbf_losses
+
+_LOSS_PARAMS = {"alpha": 1.0, "eps": 0.02, "loss_action_coef": 0.001,
+                "loss_unsafe_coef": 1.0, "loss_safe_coef": 1.0,
+                "loss_h_dot_coef": 0.1}
+
+
+def _loss_inputs(real=24, pad=8):
+    """Random order-1 rows with both mask classes present, followed by pad
+    rows of garbage (large values, masks True) that weight 0 must erase."""
+    g = torch.Generator().manual_seed(0)
+    R = real + pad
+    h = torch.randn(R, 1, generator=g)
+    h_dot = torch.randn(R, 1, generator=g)
+    actions = torch.randn(R, 2, generator=g)
+    unsafe = torch.zeros(R, dtype=torch.bool)
+    safe = torch.zeros(R, dtype=torch.bool)
+    unsafe[:7] = True
+    safe[9:real] = True
+    for t in (h, h_dot, actions):
+        t[real:] = 1e6
+    unsafe[real:] = True
+    safe[real:] = True
+    weight = torch.cat([torch.ones(real), torch.zeros(pad)])
+    return h, h_dot, actions, unsafe, safe, weight
+
+
+def test_cbf_losses_weighted_matches_unweighted():
+    """The captured engine's form (weight 1 on real rows, 0 on pad rows)
+    equals the eager form on the real rows alone, to the fp32 reordering
+    bound for sums of at most 32 terms of order 1."""
+    from gcbf_amd.algo.gcbf import cbf_losses
+    real = 24
+    h, h_dot, actions, unsafe, safe, weight = _loss_inputs(real)
+    loss_w, log_w = cbf_losses(h, h_dot, actions, unsafe, safe,
+                               _LOSS_PARAMS, weight=weight)
+    loss_e, log_e = cbf_losses(h[:real], h_dot[:real], actions[:real],
+                               unsafe[:real], safe[:real], _LOSS_PARAMS)
+    assert log_w.shape == log_e.shape == (7,)
+    assert (log_e[:4] > 0).all()          # every term is exercised
+    rtol = 32 * 2.0 ** -23
+    torch.testing.assert_close(loss_w, loss_e, rtol=rtol, atol=0)
+    torch.testing.assert_close(log_w, log_e, rtol=rtol, atol=0)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_cbf_losses_empty_mask_fallbacks(weighted):
+    """No unsafe (safe) rows: that loss is 0 and that accuracy is 1."""
+    from gcbf_amd.algo.gcbf import cbf_losses
+    real = 24
+    h, h_dot, actions, unsafe, safe, weight = _loss_inputs(real)
+    if not weighted:
+        h, h_dot, actions, unsafe, safe = (
+            t[:real] for t in (h, h_dot, actions, unsafe, safe))
+        weight = None
+    none = torch.zeros_like(unsafe)
+    _, log = cbf_losses(h, h_dot, actions, none, safe, _LOSS_PARAMS,
+                        weight=weight)
+    assert float(log[0]) == 0.0 and float(log[4]) == 1.0
+    _, log = cbf_losses(h, h_dot, actions, unsafe, none, _LOSS_PARAMS,
+                        weight=weight)
+    assert float(log[1]) == 0.0 and float(log[5]) == 1.0
+
+
+def test_macbf_degenerate_batch_size():
+    """batch_size < 10 collapses the balanced quotas (n//2 draws) to zero
+    once there is a replay memory; MACBF must then take the sampler's
+    unbalanced fallback instead of batching an empty graph list."""
+
+    class Recorder:
+        def __init__(self):
+            self.vals = []
+
+        def add_scalar(self, name, val, t):
+            self.vals.append(val)
+
+    set_seed(0)
+    dev = torch.device("cpu")
+    # MACBF's h is per edge: keep every agent in range of the others, so
+    # the only degenerate thing about the case is its batch_size
+    params = make_env("SimpleCar", 3, dev).default_params
+    params["comm_radius"] = 2 * params["area_size"]
+    env = make_env("SimpleCar", 3, dev, params=params, max_neighbors=12)
+    env.train()
+    algo = make_algo("macbf", env, 3, env.node_dim, env.edge_dim,
+                     env.action_dim, dev, batch_size=8)
+    algo.params = dict(algo.params, inner_iter=1)
+    rec = Recorder()
+    data = env.reset()
+    for step in range(1, 17):       # second update samples with a memory
+        data.update(u_ref=env.u_ref(data))
+        a = algo.step(data, prob=0.5)
+        data, r, done, info = env.step(a)
+        if done:
+            data = env.reset()
+        if algo.is_update(step):
+            assert all(g.num_edges > 0 for g in algo.buffer.data)
+            out = algo.update(step, rec)
+    assert len(rec.vals) == 2 * 7
+    assert all(np.isfinite(v) for v in rec.vals)
+    assert all(np.isfinite(v) for v in out.values())

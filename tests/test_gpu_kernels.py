@@ -734,13 +734,13 @@ def test_update_engine_matches_eager():
                 torch.stack([loss_unsafe, loss_safe, loss_h_dot,
                              loss_action]).detach())
 
-    gl = e._sample_for_warmup()
+    gl = algo._sample_batch()
     e._fill_inputs(gl)
     e.gFront.replay()
     assert int(e._ecounts.max().cpu()) <= e.E_cap
     lcap, log7 = e._graphed(e._nodes, e._uref, e._ei, e._ea, e._seg,
                             e._h_new, e.w_dev)
-    e._zero_grads()
+    algo._zero_grad()
     lcap.backward()
     g_cap = [p.grad.clone() for p in params]
     log_cap = log7[:4].clone()
@@ -768,7 +768,7 @@ def test_update_engine_matches_eager():
     assert not bad, "\n".join(bad)
 
     # and a full engine iteration must run end to end with finite logs
-    out = e.try_iter(e._sample_for_warmup())
+    out = e.try_iter(algo._sample_batch())
     assert out is not None and torch.isfinite(out).all()
 
 

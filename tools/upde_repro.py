@@ -14,6 +14,7 @@ os.environ["GCBF_AMD_UPDATE_CAPTURE_DEBUG"] = "1"
 
 from gcbf_amd.env import make_env
 from gcbf_amd.algo import make_algo
+from gcbf_amd.algo.gcbf import cbf_losses
 from gcbf_amd.graph import GraphBatch
 from gcbf_amd.rollout import RolloutEngine
 from gcbf_amd.trainer.utils import set_seed
@@ -46,9 +47,7 @@ names = [f"cbf.{n}" for n, p in algo.cbf.named_parameters()
 
 
 def eager_loss(gl):
-    """Replicate GCBF._iter_eager's loss (no optimizer step)."""
-    p = algo.params
-    eps, alpha = p["eps"], p["alpha"]
+    """GCBF._iter_eager's loss on the ring batch (no optimizer step)."""
     graphs = algo._ring.batch(gl)   # buffer snaps are metadata-only
     actions = algo.actor(graphs)
     graphs_next = env.forward_graph(graphs, actions)
@@ -56,31 +55,18 @@ def eager_loss(gl):
     h_both = algo.cbf(both)
     n_ag = h_both.shape[0] // 2
     h, h_next = h_both[:n_ag], h_both[n_ag:]
-    hv = h[:, 0]
-    um = env.unsafe_mask(graphs).to(hv.dtype)
-    cu1 = um.sum().clamp(min=1)
-    any_u = (um.sum() > 0).to(hv.dtype)
-    loss_unsafe = any_u * (torch.relu(hv + eps) * um).sum() / cu1
-    sm = env.safe_mask(graphs).to(hv.dtype)
-    cs1 = sm.sum().clamp(min=1)
-    any_s = (sm.sum() > 0).to(hv.dtype)
-    loss_safe = any_s * (torch.relu(-hv + eps) * sm).sum() / cs1
     with torch.no_grad():
         relinked = env.add_communication_links_batched(graphs_next.detach())
         h_new = algo.cbf(relinked)
     h_dot = (h_next - h) / env.dt
     residue = ((h_new - h) / env.dt - h_dot).detach()
-    h_dot = residue + h_dot
-    loss_h_dot = torch.mean(torch.relu(-h_dot - alpha * h + eps))
-    loss_action = torch.mean(torch.square(actions).sum(dim=1))
-    loss = (p["loss_unsafe_coef"] * loss_unsafe +
-            p["loss_safe_coef"] * loss_safe +
-            p["loss_h_dot_coef"] * loss_h_dot +
-            p["loss_action_coef"] * loss_action)
-    return loss, [loss_unsafe, loss_safe, loss_h_dot, loss_action]
+    loss, log7 = cbf_losses(h, residue + h_dot, actions,
+                            env.unsafe_mask(graphs), env.safe_mask(graphs),
+                            algo.params)
+    return loss, list(log7[:4])
 
 
-gl = e._sample_for_warmup()
+gl = algo._sample_batch()
 params = [p for p in algo.cbf.parameters() if p.requires_grad] + \
          [p for p in algo.actor.parameters() if p.requires_grad]
 
@@ -117,7 +103,7 @@ print("mean |a|^2 front:", a_front[:nA].pow(2).sum(1).mean().item(),
 # ---- probe 1: replayed grads vs eager grads on the SAME batch
 e._fill_inputs(gl)
 lcap, log_cap = run_graphed()
-e._zero_grads()
+algo._zero_grad()
 lcap.backward()
 g_cap = [p.grad.clone() for p in params]
 log_cap = log_cap.clone()
@@ -141,7 +127,7 @@ print(f"median cosine: {sorted(r[0] for r in rows)[len(rows)//2]:+.4f}")
 # ---- probe 2: does the captured forward see weight changes?
 for p, g in zip(params, g_cap):
     p.grad = g
-e._opt_tail()
+algo._optimizer_step()
 e._fill_inputs(gl)
 _, log_cap2 = run_graphed()
 log_cap2 = log_cap2.clone()
