@@ -522,8 +522,23 @@ class GCBF(Algorithm):
         agents already satisfying the ḣ condition under the nominal (zero)
         action fall back to it; the rest run up to 30 rounds of per-agent
         Adam descent on the ḣ violation through the frozen CBF, plus
-        exploration noise."""
+        exploration noise.
+
+        On a scene batch (``data.num_graphs > 1``, inside
+        ``SceneBatch.scenes()``) the refinement loss is the sum over graphs
+        of the per-graph mean.  Scenes do not interact, so every agent's
+        gradient, Adam state and noise scale are the single-scene ones; a
+        satisfied or finished scene has an all-false ``val`` row and is left
+        alone."""
         lr = 0.1
+        n_graphs = data.num_graphs
+        # agents of scenes that still run; None: all of them
+        live = getattr(self._env, "_live_rows", None) if n_graphs > 1 \
+            else None
+
+        def violation(h_dot):
+            val_h_dot = torch.relu(-h_dot - self.params["alpha"] * h)
+            return val_h_dot if live is None else val_h_dot * live
         h = self.cbf(data).detach()
         action = self.actor(data).detach()
         nominal = torch.zeros_like(action)
@@ -531,7 +546,7 @@ class GCBF(Algorithm):
         data_next = self._env.forward_graph(data, nominal)
         h_next = self.cbf(data_next)
         h_dot = (h_next - h) / self._env.dt
-        max_val_h_dot = torch.relu(-h_dot - self.params["alpha"] * h)
+        max_val_h_dot = violation(h_dot)
 
         ok = (max_val_h_dot[:, 0] <= 0)
         action = torch.where(ok.unsqueeze(1), nominal, action)
@@ -553,8 +568,12 @@ class GCBF(Algorithm):
             data_next = self._env.forward_graph(data, action)
             h_next = self.cbf(data_next)
             h_dot = (h_next - h) / self._env.dt
-            max_val_h_dot = torch.relu(-h_dot - self.params["alpha"] * h)
-            loss_h_dot = torch.mean(max_val_h_dot)
+            max_val_h_dot = violation(h_dot)
+            if n_graphs == 1:
+                loss_h_dot = torch.mean(max_val_h_dot)
+            else:
+                loss_h_dot = max_val_h_dot.sum() \
+                    / (max_val_h_dot.shape[0] // n_graphs)
             if loss_h_dot <= 0 or i_iter > max_iter:
                 break
             val = (max_val_h_dot[:, 0] > 0).unsqueeze(1)

@@ -8,6 +8,7 @@ from .point_agent import PointAgentEnv
 from .simple_car import SimpleCar
 from .simple_drone import SimpleDrone
 from .dubins_car import DubinsCar
+from .batched import SceneBatch
 
 
 def make_env(env: str, num_agents: int, device: torch.device, dt: float = 0.03,
@@ -30,4 +31,4 @@ def make_env(env: str, num_agents: int, device: torch.device, dt: float = 0.03,
 
 
 __all__ = ["MultiAgentEnv", "PointAgentEnv", "SimpleCar", "SimpleDrone", "DubinsCar",
-           "make_env"]
+           "SceneBatch", "make_env"]

@@ -150,16 +150,14 @@ class DubinsCar(PointAgentEnv):
         # (dubins_car.py:122-124) writes into an advanced-indexing copy and is
         # a no-op; reproduced by not zeroing.
 
-        # freeze agents that reached their goal — single-graph only: the shape
-        # check excludes batches exactly like the reference's
-        # (gcbf/env/dubins_car.py:126-132)
-        if self._obs is not None and \
-                s.shape[0] == self.num_agents + self._obs.shape[0]:
+        # freeze agents that reached their goal — the env's own scene(s)
+        # only, see _freeze_applies
+        if self._freeze_applies(s):
             am = agent_mask if agent_mask is not None else \
                 torch.ones(n_nodes, dtype=torch.bool, device=s.device)
             agent_states = s[am].reshape(-1, self.num_agents, self.state_dim)
             reach = torch.less(
-                torch.norm(agent_states[..., :2] - self._goal[:, :2], dim=-1),
+                torch.norm(agent_states[..., :2] - self._goal[..., :2], dim=-1),
                 self._params["dist2goal"]).reshape(-1)
             keep = torch.logical_not(reach).to(s.dtype).unsqueeze(1)
             frozen = xdot[am] * keep

@@ -54,6 +54,11 @@ class PointAgentEnv(MultiAgentEnv):
         self._xy_max = None
         # points whose plot limits are still owed (device-reset path)
         self._plot_pts: Optional[Tensor] = None
+        # set by SceneBatch.scenes(): number of scenes whose (B, n, G) goals
+        # and flat obstacle rows the env currently holds, and the (B*n, 1)
+        # mask of agents in scenes that are still running
+        self._scenes = 1
+        self._live_rows: Optional[Tensor] = None
 
     @property
     def agent_radius(self) -> float:
@@ -72,6 +77,14 @@ class PointAgentEnv(MultiAgentEnv):
         if data.agent_mask is not None:
             return data.states[data.agent_mask]
         return data.states
+
+    def _freeze_applies(self, states: Tensor) -> bool:
+        """Reached agents freeze only in the graph(s) the env itself holds:
+        its single scene, or inside ``SceneBatch.scenes()`` the whole scene
+        batch.  The shape check excludes update-path batches exactly like
+        the reference's (gcbf/env/dubins_car.py:126-132)."""
+        return self._obs is not None and states.shape[0] == \
+            self._scenes * self.num_agents + self._obs.shape[0]
 
     def _reached(self, agent_states: Tensor) -> Tensor:
         p = self.pos_dim
@@ -183,6 +196,19 @@ class PointAgentEnv(MultiAgentEnv):
             K = self._get_K_tensor()
         p = self._params
         return [self._step_kind, states, goal, action] \
+            + ([] if K is None else [K]) \
+            + [self.dt, p[self._radius_key], p["speed_limit"],
+               p["dist2goal"], self._action_limit]
+
+    def batched_step_args(self, states: Tensor, goal: Tensor, action: Tensor,
+                          active: Tensor, K: Optional[Tensor] = None) -> list:
+        """Argument list of ``ops.env_step_batched`` for ``(B, ·, ·)``
+        states, goals and actions and the ``(B,)`` int32 ``active`` flags —
+        the one place that knows its order."""
+        if K is None:
+            K = self._get_K_tensor()
+        p = self._params
+        return [self._step_kind, states, goal, action, active] \
             + ([] if K is None else [K]) \
             + [self.dt, p[self._radius_key], p["speed_limit"],
                p["dist2goal"], self._action_limit]

@@ -127,7 +127,7 @@ class SimpleCar(PointAgentEnv):
     # ----------------------------------------------------------------- u_ref
     def u_ref(self, data: GraphBatch) -> Tensor:
         # reference gcbf/env/simple_car.py:270-304
-        goal = torch.cat([self._goal, torch.zeros_like(self._goal)], dim=1)
+        goal = torch.cat([self._goal, torch.zeros_like(self._goal)], dim=-1)
         states = data.states.reshape(-1, self.num_agents, self.state_dim)
         diff = states - goal
 

@@ -123,11 +123,12 @@ class SimpleDrone(PointAgentEnv):
             ctrl = ctrl.masked_scatter(
                 am.unsqueeze(1).expand(-1, self.state_dim), u @ self._B.t())
         xdot = xdot + ctrl
-        if s.shape[0] == self.num_agents + self._obs.shape[0]:
-            agent_states = s[am]
+        if self._freeze_applies(s):
+            agent_states = s[am].reshape(-1, self.num_agents, self.state_dim)
             reach = torch.less(
-                torch.norm(agent_states[:, :3] - self._goal[:, :3], dim=1),
-                self._params["dist2goal"])
+                torch.norm(agent_states[..., :3] - self._goal[..., :3],
+                           dim=-1),
+                self._params["dist2goal"]).reshape(-1)
             keep = torch.logical_not(reach).to(s.dtype).unsqueeze(1)
             frozen = xdot[am] * keep
             xdot = xdot.masked_scatter(

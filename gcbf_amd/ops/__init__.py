@@ -256,6 +256,36 @@ def env_step_fused(kind: str, *args, out=None):
               out=out)
 
 
+def env_step_batched(kind: str, states: Tensor, goal: Tensor, action: Tensor,
+                     active: Tensor, *rest, out=None):
+    """Step ``B`` scenes of identical shape in one launch
+    (env_step_batched.hip; semantics in :func:`eager.env_step_batched`).
+
+    kind: "dubins" | "car" | "drone"; ``states`` (B, N, S), ``goal``
+    (B, n, G), ``action`` (B, n, A), ``active`` (B,) int32; ``rest`` is
+    ``[K,] dt, r, sl, d2g, act_lim`` (one LQR gain ``K`` shared by all
+    scenes, "car" and "drone" only).  Returns (new_states, u_ref_next,
+    reward, reach, collision, reach_all); ``out`` optionally provides those
+    six buffers.  GPU tensors run the HIP kernel, CPU tensors the eager
+    oracle.
+    """
+    if states.is_cuda:
+        ext = _require_ext(f"{kind}_step_batched")
+        if ext is not None:
+            fn = {"dubins": ext.dubins_step_batched,
+                  "car": ext.car_step_batched,
+                  "drone": ext.drone_step_batched}[kind]
+            args = (states, goal, action, active) + rest
+            return fn(*[a.contiguous() if torch.is_tensor(a) else a
+                        for a in args], out=out)
+    res = eager.env_step_batched(kind, states, goal, action, active, *rest)
+    if out is not None:
+        for buf, val in zip(out, res):
+            buf.copy_(val)
+        return list(out)
+    return list(res)
+
+
 # env kinds understood by the fused mask kernel (mirrors masks.hip)
 ENV_CAR = 0
 ENV_DUBINS = 1

@@ -203,3 +203,127 @@ def reset_sample(cand: Tensor, min_sep: Tensor, avoid: Tensor,
     pts.copy_(pts_c.to(dev))
     count.copy_(count_c.to(dev))
     return used.to(dev), min_gap
+
+
+# --------------------------------------------------------------------------
+# batched environment step (oracle of env_step_batched.hip)
+# --------------------------------------------------------------------------
+
+def _dubins_u_ref(s: Tensor, g: Tensor, sl: float) -> Tensor:
+    """PID reference controller on (..., 4) states and goals."""
+    two_pi = 2 * torch.pi
+    # op for op the envs' own u_ref (env/dubins_car.py), so that the CPU
+    # paths agree to the bit: the heading controller flips sign on a
+    # rounding difference and an episode would amplify it
+    diff = s - g
+    dist = torch.norm(diff[..., :2], dim=-1)
+    theta_t = (torch.acos(torch.clamp(-diff[..., 0] / (dist + 1e-4), -1, 1))
+               * torch.sign(-diff[..., 1])) % two_pi
+    theta = s[..., 2] % two_pi
+    td = theta_t - theta
+    agent_dir = torch.stack([torch.cos(theta), torch.sin(theta)], dim=-1)
+    inner = (-diff[..., :2] * agent_dir).sum(dim=-1)
+    between = torch.acos(torch.clamp(inner / (dist + 1e-4), -1, 1))
+    anti = (td < torch.pi) & (td >= 0)
+    clock = (td > -torch.pi) & (td <= 0)
+    one = torch.ones_like(theta)
+    sign = torch.where(theta <= torch.pi, torch.where(anti, one, -one),
+                       torch.where(clock, -one, one))
+    omega = torch.clamp(sign * 0.2 * between, -5.0, 5.0)
+    v = s[..., 3]
+    a = -0.6 * v + 0.3 * dist
+    a = torch.where(v > sl, torch.clamp(a, max=0.0), a)
+    a = torch.where(v < -sl, torch.clamp(a, min=0.0), a)
+    return torch.stack([omega, a], dim=-1)
+
+
+def _lqr_u_ref(s: Tensor, goal_full: Tensor, K: Tensor, sl: float,
+               vel: slice, gain: float) -> Tensor:
+    """-K (x - goal) minus the over-speed penalty, on (..., S) states."""
+    u = -torch.einsum("us,...s->...u", K, s - goal_full)
+    v = s[..., vel]
+    speed = v.norm(dim=-1, keepdim=True)
+    penalty = torch.relu(speed - sl) * gain
+    return u - penalty * (v / speed.clamp(min=1e-12))
+
+
+# per kind: position dims, reach / collision / step reward, action cost and
+# whether that cost is one sum over the scene's agents
+_STEP_CONST = {
+    "dubins": (2, 10.0, 0.1, -1e-4, 0.01, True),
+    "car": (2, 4.0, 2.0, -0.01, 1e-4, False),
+    "drone": (3, 10.0, 1.0, -0.01, 1e-3, False),
+}
+
+
+def env_step_batched(kind: str, states: Tensor, goal: Tensor, action: Tensor,
+                     active: Tensor, *rest):
+    """Step ``B`` scenes of identical shape at once, fp32, vectorised.
+
+    ``states`` (B, N, S), ``goal`` (B, n, G), ``action`` (B, n, A),
+    ``active`` (B,) int32; ``rest`` is ``[K,] dt, r, sl, d2g, act_lim`` with
+    the LQR gain ``K`` for "car" and "drone" only.  Returns
+    ``(new_states, u_ref_next, reward (B, n), reach (B, n), collision
+    (B, n), reach_all (B,))``.  An active scene is stepped as the env's own
+    ``step`` does it (agents freeze on reach in "dubins" and "drone",
+    obstacles drift or stay, the Dubins action cost sums the scene's own
+    agents).  An inactive scene keeps its states bit for bit, reports the
+    u_ref and the reach test of that unchanged state, reward 0 and no
+    collision.
+    """
+    if kind == "dubins":
+        K = None
+        dt, r, sl, d2g, act_lim = rest
+    else:
+        K, dt, r, sl, d2g, act_lim = rest
+    p, reach_rew, coll_rew, step_rew, act_cost, summed = _STEP_CONST[kind]
+    B, N, S = states.shape
+    n = action.shape[1]
+    on = (active != 0).view(B, 1)
+    s = states[:, :n]
+
+    def u_ref(x):
+        if kind == "dubins":
+            return _dubins_u_ref(x, goal, sl)
+        if kind == "car":
+            return _lqr_u_ref(x, torch.cat(
+                [goal, torch.zeros_like(goal)], dim=-1), K, sl,
+                slice(2, 4), 50.0)
+        return _lqr_u_ref(x, goal, K, sl, slice(3, 6), 10.0)
+
+    def reached(x):
+        return (x[..., :p] - goal[..., :p]).norm(dim=-1) < d2g
+
+    u = torch.clamp(action + u_ref(s), -act_lim, act_lim)
+    prev = reached(s)
+    xdot = torch.zeros_like(states)
+    if kind == "dubins":
+        vc = torch.clamp(states[..., 3], max=sl)
+        xdot[..., 0] = vc * torch.cos(states[..., 2])
+        xdot[..., 1] = vc * torch.sin(states[..., 2])
+        xdot[:, :n, 2] = u[..., 0] * 10
+        xdot[:, :n, 3] = u[..., 1]
+    elif kind == "car":
+        xdot[..., :2] = states[..., 2:]
+        xdot[..., 2:] = u
+    else:
+        damp = states.new_tensor([1.1, 1.1, 6.0])
+        xdot[:, :n, :3] = s[..., 3:]
+        xdot[:, :n, 3:] = -damp * s[..., 3:] + damp * u
+    if kind != "car":  # agents freeze on reach
+        xdot[:, :n] = xdot[:, :n] * (~prev).to(states.dtype).unsqueeze(-1)
+    stepped = states + xdot * dt
+    new_states = torch.where(on.unsqueeze(-1), stepped, states)
+
+    ns = new_states[:, :n]
+    reach = reached(ns)
+    dist = (ns[:, :, None, :p] - new_states[:, None, :, :p]).norm(dim=-1)
+    eye = torch.eye(N, device=states.device, dtype=dist.dtype)[:n]
+    collision = ((dist + eye * (2 * r + 1)) < 2 * r).any(dim=2) & on
+    cost = action.norm(dim=-1)
+    if summed:
+        cost = cost.sum(dim=1, keepdim=True)
+    reward = (reach.int() - prev.int()) * reach_rew \
+        - collision.int() * coll_rew + step_rew - cost * act_cost
+    reward = torch.where(on, reward, torch.zeros_like(reward))
+    return new_states, u_ref(ns), reward, reach, collision, reach.all(dim=1)

@@ -62,6 +62,25 @@ extern "C" void launch_drone_step(const float* states, const float* goal,
                                   float r, float sl, float d2g,
                                   float act_lim, hipStream_t stream);
 
+extern "C" void launch_dubins_step_batched(
+        const float* states, const float* goal, const float* action,
+        const int* active, float* new_states, float* u_ref_next,
+        float* reward, bool* reach, bool* collision, bool* reach_all, int B,
+        int N, int n, float dt, float r, float sl, float d2g, float act_lim,
+        hipStream_t stream);
+extern "C" void launch_car_step_batched(
+        const float* states, const float* goal, const float* action,
+        const int* active, const float* K, float* new_states,
+        float* u_ref_next, float* reward, bool* reach, bool* collision,
+        bool* reach_all, int B, int N, float dt, float r, float sl,
+        float d2g, float act_lim, hipStream_t stream);
+extern "C" void launch_drone_step_batched(
+        const float* states, const float* goal, const float* action,
+        const int* active, const float* K, float* new_states,
+        float* u_ref_next, float* reward, bool* reach, bool* collision,
+        bool* reach_all, int B, int N, int n, float dt, float r, float sl,
+        float d2g, float act_lim, hipStream_t stream);
+
 extern "C" void launch_reset_sample(const float* cand, const float* min_sep,
                                     const float* avoid, float avoid_dist,
                                     float* pts, int* count, int* used, int B,
@@ -360,6 +379,131 @@ std::vector<torch::Tensor> drone_step(
     return out;
 }
 
+// ---- batched step (env_step_batched.hip): B scenes of identical shape
+#define CHECK_F32(x, ...)                                              \
+    CHECK_IN(x);                                                       \
+    TORCH_CHECK(x.scalar_type() == torch::kFloat32, #x " must be fp32"); \
+    TORCH_CHECK(x.sizes() == torch::IntArrayRef({__VA_ARGS__}),        \
+                #x " has shape ", x.sizes(), ", expected {" #__VA_ARGS__ "}")
+#define CHECK_BOOL(x, ...)                                             \
+    CHECK_IN(x);                                                       \
+    TORCH_CHECK(x.scalar_type() == torch::kBool, #x " must be bool");  \
+    TORCH_CHECK(x.sizes() == torch::IntArrayRef({__VA_ARGS__}),        \
+                #x " has shape ", x.sizes(), ", expected {" #__VA_ARGS__ "}")
+
+// checks the inputs every batched step shares and returns the six output
+// buffers {new_states, u_ref_next, reward, reach, collision, reach_all}
+static std::vector<torch::Tensor> batched_step_io(
+        const torch::Tensor& states, const torch::Tensor& goal,
+        const torch::Tensor& action, const torch::Tensor& active, int64_t S,
+        int64_t G, int64_t A,
+        const c10::optional<std::vector<torch::Tensor>>& out_opt) {
+    TORCH_CHECK(states.dim() == 3 && action.dim() == 3,
+                "states (B, N, S) and action (B, n, A) expected");
+    const int64_t B = states.size(0), N = states.size(1),
+                  n = action.size(1);
+    TORCH_CHECK(n >= 1 && n <= N, "need 1 <= n <= N, got n=", n, " N=", N);
+    TORCH_CHECK(B <= 65535, "at most 65535 scenes per launch, got ", B);
+    TORCH_CHECK(N * S < (int64_t(1) << 31), "scene too large");
+    CHECK_F32(states, B, N, S);
+    CHECK_F32(goal, B, n, G);
+    CHECK_F32(action, B, n, A);
+    CHECK_IN(active);
+    TORCH_CHECK(active.scalar_type() == torch::kInt32 &&
+                active.dim() == 1 && active.size(0) == B,
+                "active must be int32 of shape (B,)");
+    if (out_opt.has_value()) {
+        TORCH_CHECK(out_opt->size() == 6, "out must be {new_states, "
+                    "u_ref_next, reward, reach, collision, reach_all}");
+        const auto& new_states = (*out_opt)[0];
+        const auto& u_ref_next = (*out_opt)[1];
+        const auto& reward = (*out_opt)[2];
+        const auto& reach = (*out_opt)[3];
+        const auto& collision = (*out_opt)[4];
+        const auto& reach_all = (*out_opt)[5];
+        CHECK_F32(new_states, B, N, S);
+        CHECK_F32(u_ref_next, B, n, A);
+        CHECK_F32(reward, B, n);
+        CHECK_BOOL(reach, B, n);
+        CHECK_BOOL(collision, B, n);
+        CHECK_BOOL(reach_all, B);
+        TORCH_CHECK(new_states.data_ptr() != states.data_ptr(),
+                    "new_states must not alias states");
+        return *out_opt;
+    }
+    auto f = states.options();
+    auto b = states.options().dtype(torch::kBool);
+    return {torch::empty_like(states), torch::empty({B, n, A}, f),
+            torch::empty({B, n}, f), torch::empty({B, n}, b),
+            torch::empty({B, n}, b), torch::empty({B}, b)};
+}
+
+std::vector<torch::Tensor> dubins_step_batched(
+        torch::Tensor states, torch::Tensor goal, torch::Tensor action,
+        torch::Tensor active, double dt, double r, double sl, double d2g,
+        double act_lim,
+        c10::optional<std::vector<torch::Tensor>> out_opt = c10::nullopt) {
+    auto out = batched_step_io(states, goal, action, active, 4, 4, 2,
+                               out_opt);
+    const int64_t B = states.size(0);
+    if (B > 0)
+        launch_dubins_step_batched(
+            states.data_ptr<float>(), goal.data_ptr<float>(),
+            action.data_ptr<float>(), active.data_ptr<int>(),
+            out[0].data_ptr<float>(), out[1].data_ptr<float>(),
+            out[2].data_ptr<float>(), out[3].data_ptr<bool>(),
+            out[4].data_ptr<bool>(), out[5].data_ptr<bool>(), (int)B,
+            (int)states.size(1), (int)action.size(1), (float)dt, (float)r,
+            (float)sl, (float)d2g, (float)act_lim, current_stream());
+    return out;
+}
+
+std::vector<torch::Tensor> car_step_batched(
+        torch::Tensor states, torch::Tensor goal, torch::Tensor action,
+        torch::Tensor active, torch::Tensor K, double dt, double r,
+        double sl, double d2g, double act_lim,
+        c10::optional<std::vector<torch::Tensor>> out_opt = c10::nullopt) {
+    auto out = batched_step_io(states, goal, action, active, 4, 2, 2,
+                               out_opt);
+    const int64_t B = states.size(0);
+    TORCH_CHECK(states.size(1) == action.size(1),
+                "SimpleCar has no obstacle rows: N must equal n");
+    CHECK_F32(K, 2, 4);
+    if (B > 0)
+        launch_car_step_batched(
+            states.data_ptr<float>(), goal.data_ptr<float>(),
+            action.data_ptr<float>(), active.data_ptr<int>(),
+            K.data_ptr<float>(), out[0].data_ptr<float>(),
+            out[1].data_ptr<float>(), out[2].data_ptr<float>(),
+            out[3].data_ptr<bool>(), out[4].data_ptr<bool>(),
+            out[5].data_ptr<bool>(), (int)B, (int)states.size(1), (float)dt,
+            (float)r, (float)sl, (float)d2g, (float)act_lim,
+            current_stream());
+    return out;
+}
+
+std::vector<torch::Tensor> drone_step_batched(
+        torch::Tensor states, torch::Tensor goal, torch::Tensor action,
+        torch::Tensor active, torch::Tensor K, double dt, double r,
+        double sl, double d2g, double act_lim,
+        c10::optional<std::vector<torch::Tensor>> out_opt = c10::nullopt) {
+    auto out = batched_step_io(states, goal, action, active, 6, 6, 3,
+                               out_opt);
+    const int64_t B = states.size(0);
+    CHECK_F32(K, 3, 6);
+    if (B > 0)
+        launch_drone_step_batched(
+            states.data_ptr<float>(), goal.data_ptr<float>(),
+            action.data_ptr<float>(), active.data_ptr<int>(),
+            K.data_ptr<float>(), out[0].data_ptr<float>(),
+            out[1].data_ptr<float>(), out[2].data_ptr<float>(),
+            out[3].data_ptr<bool>(), out[4].data_ptr<bool>(),
+            out[5].data_ptr<bool>(), (int)B, (int)states.size(1),
+            (int)action.size(1), (float)dt, (float)r, (float)sl, (float)d2g,
+            (float)act_lim, current_stream());
+    return out;
+}
+
 torch::Tensor reset_sample(torch::Tensor cand, torch::Tensor min_sep,
                            torch::Tensor avoid, double avoid_dist,
                            torch::Tensor pts, torch::Tensor count) {
@@ -414,6 +558,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("states"), py::arg("goal"), py::arg("action"),
           py::arg("K"), py::arg("dt"), py::arg("r"), py::arg("sl"),
           py::arg("d2g"), py::arg("act_lim"), py::arg("out") = py::none());
+    m.def("dubins_step_batched", &dubins_step_batched,
+          "DubinsCar step of B scenes in one launch",
+          py::arg("states"), py::arg("goal"), py::arg("action"),
+          py::arg("active"), py::arg("dt"), py::arg("r"), py::arg("sl"),
+          py::arg("d2g"), py::arg("act_lim"), py::arg("out") = py::none());
+    m.def("car_step_batched", &car_step_batched,
+          "SimpleCar step of B scenes in one launch",
+          py::arg("states"), py::arg("goal"), py::arg("action"),
+          py::arg("active"), py::arg("K"), py::arg("dt"), py::arg("r"),
+          py::arg("sl"), py::arg("d2g"), py::arg("act_lim"),
+          py::arg("out") = py::none());
+    m.def("drone_step_batched", &drone_step_batched,
+          "SimpleDrone step of B scenes in one launch",
+          py::arg("states"), py::arg("goal"), py::arg("action"),
+          py::arg("active"), py::arg("K"), py::arg("dt"), py::arg("r"),
+          py::arg("sl"), py::arg("d2g"), py::arg("act_lim"),
+          py::arg("out") = py::none());
     m.def("segment_attn_fwd", &segment_attn_fwd,
           "fused scatter-softmax + weighted scatter-sum (forward)");
     m.def("segment_attn_bwd", &segment_attn_bwd,

@@ -26,13 +26,15 @@ class Trainer:
 
     def __init__(self, env: MultiAgentEnv, env_test: MultiAgentEnv,
                  algo: Algorithm, log_dir: str, rank: int = 0,
-                 world_size: int = 1):
+                 world_size: int = 1, eval_batch: bool = False):
         self.env = env
         self.env_test = env_test
         self.algo = algo
         self.log_dir = log_dir
         self.rank = rank
         self.world_size = world_size
+        # opt-in: run the eval episodes as one SceneBatch
+        self.eval_batch = eval_batch
 
         if rank == 0:
             os.makedirs(log_dir, exist_ok=True)
@@ -140,6 +142,8 @@ class Trainer:
 
     def eval(self, step: int, eval_epi: int) -> Tuple[float, dict]:
         # reference gcbf/trainer/trainer.py:95-141
+        if self.eval_batch:
+            return self._eval_batched(step, eval_epi)
         rewards = []
         safe_rate = []
         reach = torch.zeros(self.env_test.num_agents)
@@ -169,3 +173,19 @@ class Trainer:
         return float(np.mean(rewards)), {
             "safe": round(float(np.mean(safe_rate)), 2),
             "reach": round(float(torch.mean(reach.float())), 2)}
+
+    def _eval_batched(self, step: int, eval_epi: int) -> Tuple[float, dict]:
+        """The eval episodes as one SceneBatch; same scalars and returned
+        dict as the sequential loop.  The layouts are drawn from seeds taken
+        off the global RNG, and "reach" is the last episode's, as there."""
+        from .utils import eval_ctrl_batched
+        self.algo._env = self.env_test
+        seeds = [int(np.random.randint(100000)) for _ in range(eval_epi)]
+        rewards, _, info = eval_ctrl_batched(
+            self.algo.apply, self.env_test, seeds, verbose=False)
+        self.writer.add_scalar("test/reward", float(np.mean(rewards)), step)
+        self.writer.add_scalar("test/safe_rate",
+                               float(np.mean(info["safe"])), step)
+        return float(np.mean(rewards)), {
+            "safe": round(float(np.mean(info["safe"])), 2),
+            "reach": round(float(info["reach"][-1]), 2)}

@@ -133,6 +133,61 @@ def eval_ctrl_epi(controller: Callable, env: MultiAgentEnv, seed: int = 0,
         "states": states}
 
 
+def eval_ctrl_batched(controller: Callable, env: MultiAgentEnv, seeds,
+                      verbose: bool = True, max_steps: Optional[int] = None,
+                      return_states: bool = False
+                      ) -> Tuple[list, list, dict]:
+    """Evaluate a controller on ``len(seeds)`` episodes at once, as one
+    :class:`gcbf_amd.env.SceneBatch` (one batched step kernel and one graph
+    build per step for all of them).
+
+    Episode ``b`` starts from the layout ``eval_ctrl_epi(..., seed=seeds[b])``
+    starts from, and the figures are defined as there: reward is the sum of
+    the per-step mean reward, safe the share of agents that never collided,
+    reach the share inside their goal at the episode's last step, success
+    ``reach_last & never_collided``.  ``max_steps`` caps the episodes.
+    Returns ``(rewards, lengths, info)`` with one entry per episode in each
+    list and in ``info["safe" | "reach" | "success"]``; with
+    ``return_states`` also ``info["states"]``, the ``(T_b, n, S)`` agent
+    trajectories.  The host is asked for completion once per step.
+    """
+    from ..env.batched import SceneBatch
+    batch = SceneBatch(env, len(seeds))
+    data = batch.reset(seeds)
+    n = env.num_agents
+    traj = []
+    steps = 0
+    with batch.scenes():
+        while True:
+            action = controller(data)
+            if return_states:
+                traj.append(batch.states[:, :n])
+            data, _, _, _ = batch.step(action)
+            steps += 1
+            if batch.all_done() or \
+                    (max_steps is not None and steps >= max_steps):
+                break
+    safe_agent = torch.logical_not(batch.collided)
+    success_agent = torch.logical_and(batch.reach_last, safe_agent)
+    rewards = batch.reward_sum.cpu().tolist()
+    lengths = [float(x) for x in batch.length.cpu().tolist()]
+    counts = torch.stack([safe_agent.sum(dim=1), batch.reach_last.sum(dim=1),
+                          success_agent.sum(dim=1)]).cpu().tolist()
+    info = {key: [c / n for c in row]
+            for key, row in zip(("safe", "reach", "success"), counts)}
+    if return_states:
+        states = torch.stack(traj).cpu()             # (T, B, n, S)
+        info["states"] = [states[:int(lengths[b]), b]
+                          for b in range(len(seeds))]
+    if verbose:
+        for b in range(len(seeds)):
+            print(f"n: {n}, reward: {rewards[b]:.2f}, length: {lengths[b]}, "
+                  f"safe: {info['safe'][b]:.2f}, "
+                  f"reach: {info['reach'][b]:.2f}, "
+                  f"success: {info['success'][b]:.2f}")
+    return rewards, lengths, info
+
+
 def plot_cbf_contour(cbf_fun, data: GraphBatch, env: MultiAgentEnv,
                      agent_id: int, x_dim: int, y_dim: int,
                      attention: bool = True):

@@ -13,7 +13,8 @@ import torch
 
 from gcbf_amd.algo import make_algo
 from gcbf_amd.env import make_env
-from gcbf_amd.trainer.utils import eval_ctrl_epi, read_settings, set_seed
+from gcbf_amd.trainer.utils import eval_ctrl_batched, eval_ctrl_epi, \
+    read_settings, set_seed
 
 
 def _write_video(frames, path_mp4: str):
@@ -39,6 +40,29 @@ def _write_video(frames, path_mp4: str):
         npz_path = path_mp4.replace(".mp4", ".npz")
         np.savez_compressed(npz_path, frames=np.stack(frames))
         return npz_path
+
+
+def _eval_batched(apply_fn, env, args):
+    """The --epi episodes in chunks of --batch-epi scenes.  The seeds follow
+    the recurrence the sequential loop produces (each episode seeds the
+    global RNG, the next seed is drawn from it), so both paths evaluate the
+    same layouts."""
+    seeds = []
+    for _ in range(args.epi):
+        seeds.append(np.random.randint(100000))
+        set_seed(seeds[-1])
+    rewards, lengths, info = [], [], []
+    for lo in range(0, args.epi, args.batch_epi):
+        chunk = seeds[lo:lo + args.batch_epi]
+        print(f"epi: {lo}..{lo + len(chunk) - 1}")
+        rew, length, res = eval_ctrl_batched(
+            apply_fn, env, chunk, return_states=True)
+        rewards += rew
+        lengths += length
+        info += [{"safe": res["safe"][b], "reach": res["reach"][b],
+                  "success": res["success"][b], "states": res["states"][b]}
+                 for b in range(len(chunk))]
+    return tuple(rewards), tuple(lengths), (), tuple(info)
 
 
 def test(args):
@@ -107,15 +131,18 @@ def test(args):
         return algo.apply(data, rand=args.rand)
 
     start_time = time.time()
-    results = []
-    for i in range(args.epi):
-        print(f"epi: {i}")
-        results.append(eval_ctrl_epi(apply_fn, env,
-                                     np.random.randint(100000),
-                                     not args.no_video,
-                                     plot_edge=not args.no_edge))
-    rewards, lengths, video, info = zip(*results)
-    video = sum(video, ())
+    if args.batch_epi:
+        rewards, lengths, video, info = _eval_batched(apply_fn, env, args)
+    else:
+        results = []
+        for i in range(args.epi):
+            print(f"epi: {i}")
+            results.append(eval_ctrl_epi(apply_fn, env,
+                                         np.random.randint(100000),
+                                         not args.no_video,
+                                         plot_edge=not args.no_edge))
+        rewards, lengths, video, info = zip(*results)
+        video = sum(video, ())
 
     safe_rates, reach_rates, success_rates = [], [], []
     n_traj = 0
@@ -191,4 +218,12 @@ if __name__ == "__main__":
     parser.add_argument("--device-reset", action="store_true", default=False,
                         help="sample episode resets on the device (HIP "
                              "rejection-sampling kernel; device RNG stream)")
-    test(parser.parse_args())
+    parser.add_argument("--batch-epi", type=int, default=0, metavar="B",
+                        help="evaluate the episodes B at a time as one scene "
+                             "batch (batched step kernel); needs --no-video")
+    args = parser.parse_args()
+    if args.batch_epi < 0:
+        parser.error("--batch-epi must be positive")
+    if args.batch_epi and not args.no_video:
+        parser.error("--batch-epi renders no frames: pass --no-video")
+    test(args)

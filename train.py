@@ -97,7 +97,8 @@ def train(args):
         algo.grad_sync = make_grad_synchronizer([algo.cbf, algo.actor])
 
     trainer = Trainer(env=env, env_test=env_test, algo=algo, log_dir=log_path,
-                      rank=rank, world_size=world_size)
+                      rank=rank, world_size=world_size,
+                      eval_batch=args.eval_batch)
     start_step = 1
     if args.resume is not None:
         model_dir = os.path.join(log_path, "models")
@@ -141,4 +142,7 @@ if __name__ == "__main__":
     parser.add_argument("--device-reset", action="store_true", default=False,
                         help="sample episode resets on the device (HIP "
                              "rejection-sampling kernel; device RNG stream)")
+    parser.add_argument("--eval-batch", action="store_true", default=False,
+                        help="run the --eval-epi evaluation episodes as one "
+                             "scene batch (batched step kernel)")
     train(parser.parse_args())
