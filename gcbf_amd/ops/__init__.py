@@ -310,6 +310,53 @@ def fused_masks(states: Tensor, batch: int, n_rec: int, radius: float,
 
 
 # --------------------------------------------------------------------------
+# rollout tail: mask -> env step -> padded graph rebuild -> flags, one launch
+# --------------------------------------------------------------------------
+
+_TAIL_KIND = {"car": ENV_CAR, "dubins": ENV_DUBINS, "drone": ENV_DRONE}
+
+
+def rollout_tail_supported(n_rec: int, num_nodes: int) -> bool:
+    """True where the extension is built and the scene fits the single
+    workgroup of rollout_tail.hip (bound in docs/KERNELS.md)."""
+    ext = _load_ext()
+    if ext is None or not hasattr(ext, "rollout_tail"):
+        return False
+    max_rows, max_nodes = ext.rollout_tail_bounds()
+    return 1 <= n_rec <= max_rows and num_nodes <= max_nodes
+
+
+def rollout_tail(step_args, n_rec: int, comm_radius: float, attr_kind: int,
+                 attr_dim: int, E_max: int, out, threads: int = 1024) -> None:
+    """Everything a captured rollout step does after the actor, in one
+    launch (rollout_tail.hip), bit-equal to the kernel sequence
+
+        fused_masks(states, 1, n_rec, r, kind, "unsafe").any()
+        env_step_fused(*step_args)
+        _C.build_graph_padded(new_states[:, :pos_dim], new_states, 1, n_rec,
+                              comm_radius, -1, attr_kind, attr_dim, E_max)
+        reach.all()
+
+    ``step_args`` is ``env.fused_step_args(...)``.  ``out`` is [new_states,
+    u_ref_next, reward, reach, collision, edge_index (2, E_max), seg
+    (E_max,), edge_attr (E_max, attr_dim), flags int32 (3,)]; flags receives
+    [edge_count, all(reach), unsafe_any].  GPU only: there is no eager twin,
+    callers keep the kernel sequence where this op does not apply.
+    """
+    ext = _require_ext("rollout_tail")
+    if ext is None:
+        raise RuntimeError("rollout_tail needs the HIP extension")
+    kind, states, goal, action, *rest = step_args
+    K = rest[0] if torch.is_tensor(rest[0]) else None
+    dt, r, sl, d2g, act_lim = rest[-5:]
+    ext.rollout_tail(_TAIL_KIND[kind], states.contiguous(), goal.contiguous(),
+                     action.contiguous(),
+                     None if K is None else K.contiguous(), dt, r, sl,
+                     d2g, act_lim, n_rec, float(comm_radius), int(attr_kind),
+                     int(attr_dim), int(E_max), list(out), threads)
+
+
+# --------------------------------------------------------------------------
 # episode reset
 # --------------------------------------------------------------------------
 

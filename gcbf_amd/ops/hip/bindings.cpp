@@ -87,6 +87,17 @@ extern "C" void launch_reset_sample(const float* cand, const float* min_sep,
                                     int C, int A, int n, int dim,
                                     hipStream_t stream);
 
+extern "C" int rollout_tail_max_rows();
+extern "C" int rollout_tail_max_nodes();
+extern "C" void launch_rollout_tail(
+        int kind, const float* states_in, const float* goal,
+        const float* action, const float* K, float* states_out,
+        float* u_ref_next, float* reward, bool* reach, bool* collision,
+        long* edge_index, long* seg, float* edge_attr, int* flags, int N,
+        int n, int n_rec, int S, int P, float dt, float r_agent, float sl,
+        float d2g, float act_lim, float r_comm, int attr_kind, int A_attr,
+        long E_max, int threads, hipStream_t stream);
+
 namespace {
 
 #define CHECK_IN(x)                                                    \
@@ -541,6 +552,88 @@ torch::Tensor reset_sample(torch::Tensor cand, torch::Tensor min_sep,
     return used;
 }
 
+// ---- rollout tail (rollout_tail.hip): mask -> step -> graph rebuild ->
+// flags of one scene in one single-workgroup launch
+std::vector<int64_t> rollout_tail_bounds() {
+    return {rollout_tail_max_rows(), rollout_tail_max_nodes()};
+}
+
+void rollout_tail(int64_t kind, torch::Tensor states, torch::Tensor goal,
+                  torch::Tensor action, c10::optional<torch::Tensor> K,
+                  double dt, double r, double sl, double d2g, double act_lim,
+                  int64_t n_rec, double comm_radius, int64_t attr_kind,
+                  int64_t attr_dim, int64_t E_max,
+                  std::vector<torch::Tensor> out, int64_t threads) {
+    // kinds as in masks.hip: 0 car, 1 dubins, 2 drone
+    TORCH_CHECK(kind >= 0 && kind <= 2, "rollout_tail: unknown env kind ",
+                kind);
+    const int64_t S = kind == 2 ? 6 : 4, P = kind == 2 ? 3 : 2;
+    const int64_t A = kind == 2 ? 3 : 2, G = kind == 0 ? 2 : S;
+    TORCH_CHECK(states.dim() == 2 && action.dim() == 2,
+                "rollout_tail: states (N, S) and action (n, A) expected");
+    const int64_t N = states.size(0), n = action.size(0);
+    CHECK_F32(states, N, S);
+    CHECK_F32(goal, n, G);
+    CHECK_F32(action, n, A);
+    TORCH_CHECK(n >= 1 && n <= N && (kind != 0 || n == N),
+                "rollout_tail: bad agent count ", n, " for ", N, " nodes");
+    const float* kptr = nullptr;
+    if (kind != 1) {
+        TORCH_CHECK(K.has_value(), "rollout_tail: this env needs the gain K");
+        const torch::Tensor& Kt = K.value();
+        CHECK_F32(Kt, A, S);
+        kptr = Kt.data_ptr<float>();
+    }
+    TORCH_CHECK(n_rec >= 1 && n_rec <= n,
+                "rollout_tail: n_rec must be in [1, n]");
+    TORCH_CHECK(n_rec <= rollout_tail_max_rows() &&
+                N <= rollout_tail_max_nodes(),
+                "rollout_tail: scene (", n_rec, " receivers, ", N,
+                " nodes) above the single-workgroup bound (",
+                rollout_tail_max_rows(), ", ", rollout_tail_max_nodes(), ")");
+    TORCH_CHECK((attr_kind == 0 && attr_dim == S) ||
+                (attr_kind == 1 && S == 4 && attr_dim == 5),
+                "rollout_tail: attr_kind/attr_dim mismatch");
+    TORCH_CHECK(E_max >= 0 && E_max <= n_rec * (N - 1) + 64,
+                "rollout_tail: bad E_max ", E_max);
+    TORCH_CHECK(threads == 256 || threads == 512 || threads == 1024,
+                "rollout_tail: threads must be 256, 512 or 1024");
+    TORCH_CHECK(out.size() == 9, "out must be {new_states, u_ref_next, "
+                "reward, reach, collision, edge_index, seg, edge_attr, "
+                "flags}");
+    const torch::Tensor &new_states = out[0], &u_ref_next = out[1],
+        &reward = out[2], &reach = out[3], &collision = out[4],
+        &edge_index = out[5], &seg = out[6], &edge_attr = out[7],
+        &flags = out[8];
+    CHECK_F32(new_states, N, S);
+    CHECK_F32(u_ref_next, n, A);
+    CHECK_F32(reward, n);
+    CHECK_BOOL(reach, n);
+    CHECK_BOOL(collision, n);
+    CHECK_F32(edge_attr, E_max, attr_dim);
+    CHECK_IN(edge_index); CHECK_IN(seg); CHECK_IN(flags);
+    TORCH_CHECK(edge_index.scalar_type() == torch::kInt64 &&
+                seg.scalar_type() == torch::kInt64 &&
+                edge_index.sizes() == torch::IntArrayRef({2, E_max}) &&
+                seg.sizes() == torch::IntArrayRef({E_max}),
+                "rollout_tail: edge_index (2, E_max) / seg (E_max,) int64 "
+                "expected");
+    TORCH_CHECK(flags.scalar_type() == torch::kInt32 && flags.numel() == 3,
+                "rollout_tail: flags must be int32 (3,)");
+    TORCH_CHECK(new_states.data_ptr() != states.data_ptr(),
+                "rollout_tail: new_states must not alias states");
+    launch_rollout_tail(
+        (int)kind, states.data_ptr<float>(), goal.data_ptr<float>(),
+        action.data_ptr<float>(), kptr, new_states.data_ptr<float>(),
+        u_ref_next.data_ptr<float>(), reward.data_ptr<float>(),
+        reach.data_ptr<bool>(), collision.data_ptr<bool>(),
+        edge_index.data_ptr<int64_t>(), seg.data_ptr<int64_t>(),
+        edge_attr.data_ptr<float>(), flags.data_ptr<int>(), (int)N, (int)n,
+        (int)n_rec, (int)S, (int)P, (float)dt, (float)r, (float)sl,
+        (float)d2g, (float)act_lim, (float)comm_radius, (int)attr_kind,
+        (int)attr_dim, E_max, (int)threads, current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -597,4 +690,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "greedy rejection sampling over a candidate pool (episode reset)",
           py::arg("cand"), py::arg("min_sep"), py::arg("avoid"),
           py::arg("avoid_dist"), py::arg("pts"), py::arg("count"));
+    m.def("rollout_tail", &rollout_tail,
+          "mask -> env step -> padded graph rebuild -> flags, one launch",
+          py::arg("kind"), py::arg("states"), py::arg("goal"),
+          py::arg("action"), py::arg("K"), py::arg("dt"), py::arg("r"),
+          py::arg("sl"), py::arg("d2g"), py::arg("act_lim"),
+          py::arg("n_rec"), py::arg("comm_radius"), py::arg("attr_kind"),
+          py::arg("attr_dim"), py::arg("E_max"), py::arg("out"),
+          py::arg("threads") = 1024);
+    m.def("rollout_tail_bounds", &rollout_tail_bounds,
+          "(max receiver rows, max nodes) the single-workgroup tail takes");
 }

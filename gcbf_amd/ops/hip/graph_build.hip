@@ -12,65 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cfloat>
 
-#define WAVE 64
-
-// rows per block: 4 waves, each owning one receiver row
-#define ROWS_PER_BLOCK 4
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        v = fminf(v, __shfl_down(v, off, WAVE));
-    return __shfl(v, 0, WAVE);
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        v += __shfl_down(v, off, WAVE);
-    return __shfl(v, 0, WAVE);
-}
-
-// adjusted pairwise distance: self-edge pushed out of range like the
-// reference's +eye*(r+1) trick
-__device__ __forceinline__ float row_dist(const float* __restrict__ pos,
-                                          int P, int gbase, int i, int j,
-                                          float big) {
-    const float* pi = pos + (size_t)(gbase + i) * P;
-    const float* pj = pos + (size_t)(gbase + j) * P;
-    float d2 = 0.f;
-#pragma unroll 3
-    for (int c = 0; c < P; ++c) {
-        const float t = pi[c] - pj[c];
-        d2 += t * t;
-    }
-    float d = sqrtf(d2);
-    if (i == j) d += big;
-    return d;
-}
-
-// k-th smallest adjusted distance in the row (duplicates counted), matching
-// torch.topk(k, largest=False).values[-1]
-__device__ __forceinline__ float kth_smallest(const float* __restrict__ pos,
-                                              int P, int gbase, int i, int N,
-                                              float big, int k, int lane) {
-    float kth = -FLT_MAX;
-    int remaining = k;
-    while (remaining > 0) {
-        float lmin = FLT_MAX;
-        for (int j = lane; j < N; j += WAVE) {
-            const float d = row_dist(pos, P, gbase, i, j, big);
-            if (d > kth) lmin = fminf(lmin, d);
-        }
-        const float m = wave_min(lmin);
-        int cnt = 0;
-        for (int j = lane; j < N; j += WAVE)
-            cnt += (row_dist(pos, P, gbase, i, j, big) == m);
-        remaining -= wave_sum_i(cnt);
-        kth = m;
-    }
-    return kth;
-}
+#include "graph_build_common.h"
 
 extern "C" __global__ void radius_count(
         const float* __restrict__ pos,   // (B*N, P)
@@ -81,40 +23,8 @@ extern "C" __global__ void radius_count(
     if (row >= B * n_rec) return;
     const int b = row / n_rec, i = row % n_rec;
     const int gbase = b * N;
-    const float big = r + 1.f;
-
-    float kth = FLT_MAX;
-    if (topk > 0 && topk < N)
-        kth = kth_smallest(pos, P, gbase, i, N, big, topk, lane);
-
-    int cnt = 0;
-    for (int j = lane; j < N; j += WAVE) {
-        const float d = row_dist(pos, P, gbase, i, j, big);
-        cnt += (d < r && d <= kth);
-    }
-    cnt = wave_sum_i(cnt);
+    const int cnt = count_row(pos, P, P, gbase, i, N, r, topk, lane);
     if (lane == 0) counts[row] = cnt;
-}
-
-// edge_attr kinds
-#define ATTR_DIFF 0    // states[src] - states[dst], S dims
-#define ATTR_DUBINS 1  // [x,y,th,v cos th,v sin th] diff, 5 dims
-
-__device__ __forceinline__ void write_attr(float* __restrict__ attr,
-                                           const float* __restrict__ states,
-                                           int S, int kind, long src,
-                                           long dst) {
-    const float* ss = states + (size_t)src * S;
-    const float* sd = states + (size_t)dst * S;
-    if (kind == ATTR_DIFF) {
-        for (int c = 0; c < S; ++c) attr[c] = ss[c] - sd[c];
-    } else {  // ATTR_DUBINS: S == 4 -> 5 attr dims
-        attr[0] = ss[0] - sd[0];
-        attr[1] = ss[1] - sd[1];
-        attr[2] = ss[2] - sd[2];
-        attr[3] = ss[3] * cosf(ss[2]) - sd[3] * cosf(sd[2]);
-        attr[4] = ss[3] * sinf(ss[2]) - sd[3] * sinf(sd[2]);
-    }
 }
 
 extern "C" __global__ void radius_fill(
@@ -131,37 +41,8 @@ extern "C" __global__ void radius_fill(
     if (row >= B * n_rec) return;
     const int b = row / n_rec, i = row % n_rec;
     const int gbase = b * N;
-    const float big = r + 1.f;
-
-    float kth = FLT_MAX;
-    if (topk > 0 && topk < N)
-        kth = kth_smallest(pos, P, gbase, i, N, big, topk, lane);
-
-    int base = offsets[row];
-    for (int j0 = 0; j0 < N; j0 += WAVE) {
-        const int j = j0 + lane;
-        bool pred = false;
-        if (j < N) {
-            const float d = row_dist(pos, P, gbase, i, j, big);
-            pred = (d < r && d <= kth);
-        }
-        const unsigned long long mask = __ballot(pred);
-        if (pred) {
-            const int off = base + __popcll(mask & ((1ull << lane) - 1ull));
-            // guard: with a soft capacity (padded engine buffers) the edge
-            // count can exceed E_total — skip writes; the host detects the
-            // overflow from the published count and redoes the step eagerly
-            if (off < E_total) {
-                const long src = gbase + j;
-                const long dst = gbase + i;
-                edge_index[off] = src;
-                edge_index[E_total + off] = dst;
-                write_attr(edge_attr + (size_t)off * A, states, S, attr_kind,
-                           src, dst);
-            }
-        }
-        base += __popcll(mask);
-    }
+    fill_row(pos, P, states, offsets[row], edge_index, edge_attr, E_total,
+             gbase, i, N, P, S, A, r, topk, attr_kind, lane);
 }
 
 // Pad a built edge list out to a fixed capacity so every consumer shape is
@@ -181,14 +62,7 @@ extern "C" __global__ void pad_edges(
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx == 0) *e_count = (int)E;
     if (idx >= E_max) return;
-    if (idx < E) {
-        seg[idx] = edge_index[E_max + idx];  // dst
-    } else {
-        edge_index[idx] = 0;
-        edge_index[E_max + idx] = 0;
-        seg[idx] = N_total;
-        for (int c = 0; c < A; ++c) edge_attr[idx * A + c] = 0.f;
-    }
+    pad_entry(idx, E, edge_index, seg, edge_attr, E_max, N_total, A);
 }
 
 extern "C" void launch_pad_edges(const int* offsets, const int* counts,

@@ -12,6 +12,11 @@ on ROCm) and replays it per step:
     → flag publication ([edge_count, reach_all, unsafe_any] in one int32
       tensor; the host reads it once per step)
 
+For scenes that fit one workgroup everything after the actor is a single
+launch (ops.rollout_tail, rollout_tail.hip), bit-equal to the kernel
+sequence above; larger scenes, and GCBF_AMD_ROLLOUT_TAIL=0, run the
+sequence.
+
 Static shapes come from padding: edge buffers hold E_max = n·(N−1) entries,
 pad entries carry src=dst=0 (valid gather index) and a segment sentinel
 id == num_nodes so the CSR attention aggregation skips them; the GEMMs run
@@ -23,13 +28,21 @@ without re-capture.
 """
 from __future__ import annotations
 
-
+import os
 
 import numpy as np
 import torch
 
 from . import ops
 from .graph import GraphBatch
+
+
+# Largest scene for which the engine takes the one-launch tail.  The kernel
+# itself accepts more (its LDS bound, ops.rollout_tail_supported), but one
+# workgroup only beats the multi-kernel sequence while every wave owns at
+# most two receiver rows (measurements in docs/KERNELS.md, rollout_tail).
+TAIL_MAX_ROWS = 32
+TAIL_MAX_NODES = 64
 
 
 def engine_supported(env, algo) -> bool:
@@ -105,6 +118,16 @@ class RolloutEngine:
         K = env._get_K_tensor()
         self.K = None if K is None else K.clone().contiguous()
 
+        # one-launch tail (rollout_tail.hip) for everything after the actor;
+        # GCBF_AMD_ROLLOUT_TAIL=0 keeps the multi-kernel body (read here, at
+        # construction, so one process can build both kinds of engine)
+        self.n_rec = self.n if self.agent_mask is not None else self.N
+        self._tail = (os.environ.get("GCBF_AMD_ROLLOUT_TAIL", "1") != "0"
+                      and env._max_neighbors is None
+                      and self.n_rec <= TAIL_MAX_ROWS
+                      and self.N <= TAIL_MAX_NODES
+                      and ops.rollout_tail_supported(self.n_rec, self.N))
+
         self._load_graph_from_env()
         self._capture()
         # attach the ring store up front so per-step snapshots can be
@@ -133,6 +156,16 @@ class RolloutEngine:
                 action = self.zero_action
             else:
                 action = self.algo.actor(data)
+            if self._tail:
+                ops.rollout_tail(
+                    self.env.fused_step_args(
+                        self.states[i], self.goal, action, self.K),
+                    self.n_rec, self.env.params["comm_radius"],
+                    self.env._attr_kind, self.edge_dim, self.E_max,
+                    out=[self.states[o], self.u_ref[o], self.reward_buf,
+                         self.reach_buf, self.coll_buf, self.ei[o],
+                         self.seg[o], self.ea[o], self.flags])
+                return
             unsafe_any = self.env.unsafe_mask(data).any()
             # kernels write set o directly (out= buffers), so the replay
             # has no copy-back; ecount lands straight in flags[0]

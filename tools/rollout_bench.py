@@ -1,6 +1,7 @@
 """Rollout-only microbenchmark: captured engine step cost, split by path.
 
     python tools/rollout_bench.py [--env DubinsCar] [-n 16] [--obs 0]
+                                  [--tail {0,1}]
 
 Times engine.step for forced-policy, forced-explore and mixed (prob 0.5)
 streams, without updates — isolates rollout regressions from update noise
@@ -38,8 +39,13 @@ def main():
     p.add_argument("-n", "--num-agents", type=int, default=16)
     p.add_argument("--obs", type=int, default=0)
     p.add_argument("--steps", type=int, default=1500)
+    p.add_argument("--tail", type=int, choices=(0, 1), default=None,
+                   help="force GCBF_AMD_ROLLOUT_TAIL (one-launch step tail) "
+                        "off/on for A/B runs; default: leave the env var")
     args = p.parse_args()
 
+    if args.tail is not None:
+        os.environ["GCBF_AMD_ROLLOUT_TAIL"] = str(args.tail)
     set_seed(0)
     dev = torch.device("cuda")
     e0 = make_env(args.env, args.num_agents, dev)
@@ -60,7 +66,7 @@ def main():
     t_mix = run_steps(eng, 0.5, args.steps)
     print(f"rollout ms/step: policy {t_pol:.4f}  explore {t_exp:.4f}  "
           f"mixed(0.5) {t_mix:.4f}   [{args.env} n={args.num_agents} "
-          f"obs={args.obs}]")
+          f"obs={args.obs} tail={int(eng._tail)}]")
 
 
 if __name__ == "__main__":
