@@ -44,7 +44,7 @@ class GraphBatch:
 
     __slots__ = ("x", "pos", "states", "edge_index", "edge_attr", "agent_mask",
                  "u_ref", "_ptr", "_dst_ptr", "seg_dst", "agents_first_n",
-                 "ring_id", "agent_index", "_edge_count")
+                 "ring_id", "agent_index", "_edge_count", "actor_glue")
 
     def __init__(
             self,
@@ -84,6 +84,9 @@ class GraphBatch:
         # static agent layout) — models prefer it over the boolean
         # agent_mask because integer indexing is hipGraph-capturable
         self.agent_index = None
+        # optional: caller's switch for the actor's padded-bf16 glue path
+        # (True/False; None lets the controller read GCBF_AMD_ACTOR_GLUE)
+        self.actor_glue = None
 
     # ------------------------------------------------------------------ sizes
     @property

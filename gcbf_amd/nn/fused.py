@@ -96,13 +96,75 @@ def _mirror(lin, force: bool = False):
     return lin._bf16_mirror[1], lin._bf16_mirror[2], lin._bf16_mirror[3]
 
 
+def _mirror_version(lin) -> int:
+    return lin.weight._version + (0 if lin.bias is None
+                                  else lin.bias._version)
+
+
+def _table_tensors(lin) -> list:
+    """Tensors a refresh-table row addresses: master weight, weight mirror,
+    and (bias, bf16 bias mirror, fp32 bias copy) or Nones."""
+    _, wb, bb, b32 = lin._bf16_mirror
+    return [lin.weight, wb, lin.bias, None if lin.bias is None else bb,
+            None if lin.bias is None else b32]
+
+
+def _build_mirror_table(layers: list):
+    """Device table for ``_C.refresh_mirrors`` over ``layers``, or None where
+    the one-launch refresh does not apply (CPU, no extension, a master that
+    is not plain contiguous fp32)."""
+    from .. import ops
+    cols = [_table_tensors(m) for m in layers]
+    w0 = cols[0][0]
+    if not w0.is_cuda or not ops.hip_available():
+        return None
+    for w, wb, b, bb, b32 in cols:
+        for t in (w, b):
+            if t is not None and not (t.is_cuda and t.is_contiguous()
+                                      and t.dtype == torch.float32
+                                      and t.device == w0.device):
+                return None
+    host = _ext().mirror_table(*[[c[i].detach() if c[i] is not None else None
+                                  for c in cols] for i in range(5)])
+    return {
+        "table": host.to(w0.device),
+        "layers": layers,
+        "ptrs": [t.data_ptr() for c in cols for t in c if t is not None],
+        "max_groups": max(c[1].numel() // 4 for c in cols),
+    }
+
+
 def sync_bf16_mirrors(module: torch.nn.Module):
     """Refresh every existing mirror after an optimizer step (captured
-    replays skip Python, so the refresh must be explicit; force=True
-    because fused Adam does not bump version counters)."""
-    for m in module.modules():
-        if getattr(m, "_bf16_mirror", None) is not None:
+    replays skip Python, so the refresh must be explicit; the refresh is
+    unconditional because fused Adam does not bump version counters).
+
+    On GPU all mirrors of ``module`` are refreshed by ONE launch
+    (mlp_glue.hip, refresh_mirrors) over a device table of addresses.
+    Masters and mirrors keep their storage, so the table is built once and
+    rebuilt only when a mirror appeared or an address changed.  CPU modules,
+    and anything the table cannot describe, take the per-layer path."""
+    layers = [m for m in module.modules()
+              if getattr(m, "_bf16_mirror", None) is not None]
+    if not layers:
+        return
+    state = module.__dict__.get("_mirror_table")
+    ptrs = None
+    if state is not None and len(state["layers"]) == len(layers) and all(
+            a is b for a, b in zip(state["layers"], layers)):
+        ptrs = [t.data_ptr() for m in layers for t in _table_tensors(m)
+                if t is not None]
+    if state is None or ptrs != state["ptrs"]:
+        state = _build_mirror_table(layers)
+        module.__dict__["_mirror_table"] = state
+    if state is None:
+        for m in layers:
             _mirror(m, force=True)
+        return
+    _ext().refresh_mirrors(state["table"], state["max_groups"])
+    for m in layers:
+        c = m._bf16_mirror
+        m._bf16_mirror = (_mirror_version(m), c[1], c[2], c[3])
 
 
 # ----------------------------------------------------------- autograd path
@@ -205,6 +267,26 @@ def run_plan(plan, x: Tensor, bucket: int = 256) -> Tensor:
             if last:
                 h = h.float()
     return h[:M] if Mp != M else h
+
+
+def plan_is_plain(plan, rows_padded: int) -> bool:
+    """True where :func:`run_plan_padded_bf16` applies: at this row count
+    every layer is a plain ``nn.Linear`` served by the library GEMM."""
+    return all(isinstance(lin, torch.nn.Linear)
+               and not shapes_ok(rows_padded, lin.weight.shape[0])
+               for lin, _ in plan)
+
+
+def run_plan_padded_bf16(plan, h: Tensor) -> Tensor:
+    """No-grad plan over an already row-padded bf16 input; returns the
+    padded bf16 output.  Per layer exactly what :func:`run_plan` issues in
+    no-grad mode on the library path (same GEMM call, same operands), with
+    the pad ``cat``, the entry/exit casts and the row slice left to the
+    caller, who feeds the padded bf16 rows straight into the next MLP."""
+    for lin, act in plan:
+        wb, bb, _ = _mirror(lin)
+        h = _apply_act(F.linear(h, wb[:, :lin.weight.shape[1]], bb), act)
+    return h
 
 
 def _weight_of(lin) -> Tensor:

@@ -124,6 +124,43 @@ class ControllerGNNLayer(nn.Module):
                         else gamma_in[node_mask])
         return self.gamma(gamma_in)
 
+    def glue_applies(self, x: Tensor, edge_index: Tensor, n_rows) -> bool:
+        """Whether :meth:`forward_padded_bf16` computes this call: no-grad
+        GPU inference on the library-GEMM plans with a static row count."""
+        from . import fused
+        bucket = MLP.BUCKET
+        E = edge_index.shape[1]
+        return (not torch.is_grad_enabled() and x.is_cuda
+                and isinstance(n_rows, int) and n_rows > 0 and E > 0
+                and ops.hip_available()
+                and all(m.fused_mfma and fused.plan_is_plain(
+                            m._plan, -(-rows // bucket) * bucket)
+                        for m, rows in ((self.phi, E), (self.gamma, n_rows),
+                                        (self.aggr_module.gate_nn, E))))
+
+    def forward_padded_bf16(self, x: Tensor, edge_attr: Tensor,
+                            edge_index: Tensor, n_rows: int,
+                            seg_dst: Tensor) -> Tensor:
+        """No-grad forward that never leaves padded bf16 between the GEMMs:
+        returns γ's output for the first ``n_rows`` nodes as bf16 rows
+        padded to the GEMM bucket.  Same GEMM calls on the same operand
+        values as :meth:`forward`; the gathers, cats, pads, casts, slices
+        and the CSR pointer between them are three glue kernels
+        (ops/hip/mlp_glue.hip).  φ's pad rows reach the gate MLP unzeroed:
+        GEMM rows are independent and the aggregation reads real edges
+        only."""
+        from . import fused
+        bucket = MLP.BUCKET
+        rows_e = -(-edge_index.shape[1] // bucket) * bucket
+        rows_n = -(-n_rows // bucket) * bucket
+        msg = fused.run_plan_padded_bf16(
+            self.phi._plan,
+            ops.edge_inputs_bf16(x, edge_index, edge_attr, rows_e))
+        gate = fused.run_plan_padded_bf16(self.aggr_module.gate_nn._plan, msg)
+        gamma_in = ops.attn_aggregate_gamma_in(
+            msg, gate, seg_dst, x, n_rows, x.shape[0], rows_n)
+        return fused.run_plan_padded_bf16(self.gamma._plan, gamma_in)
+
 
 class CBFNetLayer(nn.Module):
     """MACBF per-edge CBF: φ output returned per edge, no aggregation

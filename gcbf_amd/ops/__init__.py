@@ -357,6 +357,72 @@ def rollout_tail(step_args, n_rec: int, comm_radius: float, attr_kind: int,
 
 
 # --------------------------------------------------------------------------
+# MLP glue: padded bf16 GEMM inputs written directly (mlp_glue.hip)
+# --------------------------------------------------------------------------
+
+def _pad_rows(t: Tensor, rows: int) -> Tensor:
+    return t if t.shape[0] == rows else torch.cat(
+        [t, t.new_zeros(rows - t.shape[0], t.shape[1])])
+
+
+def edge_inputs_bf16(x: Tensor, edge_index: Tensor, edge_attr: Tensor,
+                     rows_padded: int) -> Tensor:
+    """bf16 (rows_padded, 2*node_dim+edge_dim): row e is ``[x[dst_e],
+    x[src_e], edge_attr[e]]`` rounded to nearest even, rows past the edge
+    capacity are zero.  One launch instead of two gathers, two cats, a
+    zero-fill and a cast."""
+    if x.is_cuda:
+        ext = _require_ext("edge_inputs_bf16")
+        if ext is not None:
+            return ext.edge_inputs_bf16(
+                x.contiguous(), edge_index.contiguous(),
+                edge_attr.contiguous(), rows_padded)
+    src, dst = edge_index[0], edge_index[1]
+    rows = torch.cat([x.index_select(0, dst), x.index_select(0, src),
+                      edge_attr], dim=1)
+    return _pad_rows(rows, rows_padded).bfloat16()
+
+
+def attn_aggregate_gamma_in(msg: Tensor, gate: Tensor, seg: Tensor,
+                            x: Tensor, n_rows: int, num_nodes: int,
+                            rows_padded: int) -> Tensor:
+    """bf16 (rows_padded, D+node_dim): row r < n_rows is the
+    softmax-weighted sum of the messages whose ``seg == r`` followed by
+    ``x[r]``; the other rows are zero.  ``msg`` is bf16 with at least
+    ``len(seg)`` rows, ``seg`` is dst-sorted with sentinel entries ==
+    ``num_nodes`` at the end.  Same fp32 arithmetic as
+    :func:`segment_attn_aggregate` (one shared device function)."""
+    if msg.is_cuda:
+        ext = _require_ext("attn_aggregate_gamma_in")
+        if ext is not None:
+            return ext.attn_aggregate_gamma_in(
+                msg.contiguous(), gate.reshape(-1).contiguous(),
+                seg.contiguous(), x.contiguous(), n_rows, num_nodes,
+                rows_padded)
+    E = seg.shape[0]
+    real = seg < num_nodes          # drop the sentinel entries
+    aggr = segment_attn_aggregate(
+        msg[:E][real].float(),
+        gate.reshape(-1)[:E][real].float().unsqueeze(-1), seg[real],
+        num_nodes)
+    rows = torch.cat([aggr, x], dim=1)[:n_rows]
+    return _pad_rows(rows, rows_padded).bfloat16()
+
+
+def rows_cat_pad_bf16(a: Tensor, b: Tensor, n_rows: int,
+                      rows_padded: int) -> Tensor:
+    """bf16 (rows_padded, Da+Db): ``[a[r], bf16(b[r])]`` for r < n_rows,
+    zero rows after.  ``a`` is bf16, ``b`` fp32."""
+    if a.is_cuda:
+        ext = _require_ext("rows_cat_pad_bf16")
+        if ext is not None:
+            return ext.rows_cat_pad_bf16(a.contiguous(), b.contiguous(),
+                                         n_rows, rows_padded)
+    rows = torch.cat([a[:n_rows], b[:n_rows].bfloat16()], dim=1)
+    return _pad_rows(rows, rows_padded)
+
+
+# --------------------------------------------------------------------------
 # episode reset
 # --------------------------------------------------------------------------
 

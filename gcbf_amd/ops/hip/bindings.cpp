@@ -98,9 +98,25 @@ extern "C" void launch_rollout_tail(
         float d2g, float act_lim, float r_comm, int attr_kind, int A_attr,
         long E_max, int threads, hipStream_t stream);
 
+extern "C" void launch_edge_inputs_bf16(const float* x, const long* ei,
+                                        const float* ea, void* out, int N,
+                                        int nd, int ed, long E, long rows,
+                                        hipStream_t stream);
+extern "C" void launch_attn_gamma_in(const void* msg, const void* gate,
+                                     int gate_is_bf16, const long* seg,
+                                     const float* x, float* att, void* out,
+                                     int E, int D, int nd, int n_rows,
+                                     int rows, hipStream_t stream);
+extern "C" void launch_rows_cat_pad_bf16(const void* a, const float* b,
+                                         void* out, int Da, int Db,
+                                         long n_rows, long rows,
+                                         hipStream_t stream);
+extern "C" void launch_refresh_mirrors(const long long* table, int n_layers,
+                                       long max_groups, hipStream_t stream);
+
 namespace {
 
-#define CHECK_IN(x)                                                    \
+#define CHECK_IN(x)                                                   \
     TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                    \
     TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
 
@@ -634,6 +650,156 @@ void rollout_tail(int64_t kind, torch::Tensor states, torch::Tensor goal,
         (int)attr_dim, E_max, (int)threads, current_stream());
 }
 
+// ---- MLP glue (mlp_glue.hip): padded bf16 GEMM inputs written directly
+torch::Tensor edge_inputs_bf16(torch::Tensor x, torch::Tensor edge_index,
+                               torch::Tensor edge_attr, int64_t rows_padded) {
+    TORCH_CHECK(x.dim() == 2 && edge_attr.dim() == 2 &&
+                edge_index.dim() == 2 && edge_index.size(0) == 2,
+                "edge_inputs_bf16: x (N, nd), edge_index (2, E), edge_attr "
+                "(E, ed) expected");
+    const int64_t N = x.size(0), nd = x.size(1);
+    const int64_t E = edge_index.size(1), ed = edge_attr.size(1);
+    CHECK_F32(x, N, nd);
+    CHECK_F32(edge_attr, E, ed);
+    CHECK_IN(edge_index);
+    TORCH_CHECK(edge_index.scalar_type() == torch::kInt64,
+                "edge_index must be int64");
+    TORCH_CHECK(rows_padded >= E, "rows_padded below the edge capacity");
+    TORCH_CHECK(N < (int64_t(1) << 31) && nd < 65536 && ed < 65536,
+                "edge_inputs_bf16: sizes out of range");
+    auto out = torch::empty({rows_padded, 2 * nd + ed},
+                            x.options().dtype(torch::kBFloat16));
+    if (out.numel() > 0)
+        launch_edge_inputs_bf16(x.data_ptr<float>(),
+                                edge_index.data_ptr<int64_t>(),
+                                edge_attr.data_ptr<float>(), out.data_ptr(),
+                                (int)N, (int)nd, (int)ed, E, rows_padded,
+                                current_stream());
+    return out;
+}
+
+torch::Tensor attn_aggregate_gamma_in(torch::Tensor msg, torch::Tensor gate,
+                                      torch::Tensor seg, torch::Tensor x,
+                                      int64_t n_rows, int64_t num_nodes,
+                                      int64_t rows_padded) {
+    CHECK_IN(msg); CHECK_IN(gate); CHECK_IN(seg); CHECK_IN(x);
+    TORCH_CHECK(msg.scalar_type() == torch::kBFloat16 && msg.dim() == 2,
+                "msg must be bf16 (rows, D)");
+    TORCH_CHECK(gate.scalar_type() == torch::kBFloat16 ||
+                gate.scalar_type() == torch::kFloat32,
+                "gate must be bf16 or fp32");
+    TORCH_CHECK(seg.scalar_type() == torch::kInt64 && seg.dim() == 1,
+                "seg must be int64 (E,)");
+    TORCH_CHECK(x.scalar_type() == torch::kFloat32 && x.dim() == 2,
+                "x must be fp32 (N, nd)");
+    const int64_t E = seg.size(0), D = msg.size(1), nd = x.size(1);
+    TORCH_CHECK(msg.size(0) >= E && gate.numel() >= E,
+                "msg and gate must cover every edge slot");
+    TORCH_CHECK(n_rows >= 0 && n_rows <= num_nodes && n_rows <= x.size(0) &&
+                n_rows <= rows_padded,
+                "attn_aggregate_gamma_in: bad n_rows ", n_rows);
+    TORCH_CHECK(E < (int64_t(1) << 31) && rows_padded < (int64_t(1) << 31) &&
+                E * D < (int64_t(1) << 40) && D + nd < (int64_t(1) << 24),
+                "attn_aggregate_gamma_in: sizes out of range");
+    auto out = torch::empty({rows_padded, D + nd}, msg.options());
+    // per-edge softmax staging; only entries inside a segment are touched
+    auto att = torch::empty({E}, x.options());
+    if (rows_padded > 0)
+        launch_attn_gamma_in(msg.data_ptr(), gate.data_ptr(),
+                             gate.scalar_type() == torch::kBFloat16 ? 1 : 0,
+                             seg.data_ptr<int64_t>(), x.data_ptr<float>(),
+                             att.data_ptr<float>(), out.data_ptr(), (int)E,
+                             (int)D, (int)nd, (int)n_rows, (int)rows_padded,
+                             current_stream());
+    return out;
+}
+
+torch::Tensor rows_cat_pad_bf16(torch::Tensor a, torch::Tensor b,
+                                int64_t n_rows, int64_t rows_padded) {
+    CHECK_IN(a); CHECK_IN(b);
+    TORCH_CHECK(a.scalar_type() == torch::kBFloat16 && a.dim() == 2,
+                "a must be bf16 (rows, Da)");
+    TORCH_CHECK(b.scalar_type() == torch::kFloat32 && b.dim() == 2,
+                "b must be fp32 (rows, Db)");
+    TORCH_CHECK(n_rows >= 0 && n_rows <= a.size(0) && n_rows <= b.size(0) &&
+                n_rows <= rows_padded, "rows_cat_pad_bf16: bad n_rows ",
+                n_rows);
+    const int64_t Da = a.size(1), Db = b.size(1);
+    TORCH_CHECK(Da + Db < (int64_t(1) << 24), "rows_cat_pad_bf16: too wide");
+    auto out = torch::empty({rows_padded, Da + Db}, a.options());
+    if (out.numel() > 0)
+        launch_rows_cat_pad_bf16(a.data_ptr(), b.data_ptr<float>(),
+                                 out.data_ptr(), (int)Da, (int)Db, n_rows,
+                                 rows_padded, current_stream());
+    return out;
+}
+
+// ---- one-launch bf16 mirror refresh (mlp_glue.hip)
+// Host table for refresh_mirrors, one row per Linear; every tensor is
+// checked here because the kernel sees only addresses.  ``biases`` entries
+// may be None, then the layer's two bias mirrors are ignored.
+torch::Tensor mirror_table(
+        std::vector<torch::Tensor> weights,
+        std::vector<torch::Tensor> mirrors,
+        std::vector<c10::optional<torch::Tensor>> biases,
+        std::vector<c10::optional<torch::Tensor>> bias_mirrors,
+        std::vector<c10::optional<torch::Tensor>> bias_copies) {
+    const size_t n = weights.size();
+    TORCH_CHECK(mirrors.size() == n && biases.size() == n &&
+                bias_mirrors.size() == n && bias_copies.size() == n,
+                "mirror_table: list lengths differ");
+    auto table = torch::zeros({(int64_t)n, 8}, torch::kInt64);
+    auto* t = table.data_ptr<int64_t>();
+    for (size_t i = 0; i < n; ++i, t += 8) {
+        const torch::Tensor& w = weights[i];
+        const torch::Tensor& wb = mirrors[i];
+        CHECK_IN(w); CHECK_IN(wb);
+        TORCH_CHECK(w.dim() == 2 && w.scalar_type() == torch::kFloat32,
+                    "mirror_table: weight must be fp32 (rows, K)");
+        const int64_t rows = w.size(0), K = w.size(1);
+        const int64_t K64 = (K + 63) / 64 * 64;
+        TORCH_CHECK(wb.scalar_type() == torch::kBFloat16 &&
+                    wb.sizes() == torch::IntArrayRef({rows, K64}),
+                    "mirror_table: mirror must be bf16 (rows, K64)");
+        TORCH_CHECK(K64 < (int64_t(1) << 31), "mirror_table: K too large");
+        t[0] = (int64_t)w.data_ptr();
+        t[1] = (int64_t)wb.data_ptr();
+        t[2] = rows; t[3] = K; t[4] = K64;
+        if (biases[i].has_value()) {
+            TORCH_CHECK(bias_mirrors[i].has_value() &&
+                        bias_copies[i].has_value(),
+                        "mirror_table: bias without mirrors");
+            const torch::Tensor& b = *biases[i];
+            const torch::Tensor& bb = *bias_mirrors[i];
+            const torch::Tensor& b32 = *bias_copies[i];
+            CHECK_F32(b, rows);
+            CHECK_F32(b32, rows);
+            CHECK_IN(bb);
+            TORCH_CHECK(bb.scalar_type() == torch::kBFloat16 &&
+                        bb.sizes() == torch::IntArrayRef({rows}),
+                        "mirror_table: bias mirror must be bf16 (rows,)");
+            TORCH_CHECK(b32.data_ptr() != b.data_ptr(),
+                        "mirror_table: bias copy aliases the master");
+            t[5] = (int64_t)b.data_ptr();
+            t[6] = (int64_t)bb.data_ptr();
+            t[7] = (int64_t)b32.data_ptr();
+        }
+    }
+    return table;
+}
+
+void refresh_mirrors(torch::Tensor table, int64_t max_groups) {
+    CHECK_IN(table);
+    TORCH_CHECK(table.scalar_type() == torch::kInt64 && table.dim() == 2 &&
+                table.size(1) == 8, "refresh_mirrors: table must be int64 "
+                "(n, 8) as built by mirror_table");
+    TORCH_CHECK(table.size(0) <= 65535, "refresh_mirrors: too many layers");
+    if (table.size(0) == 0) return;
+    launch_refresh_mirrors(
+        reinterpret_cast<const long long*>(table.data_ptr<int64_t>()),
+        (int)table.size(0), max_groups, current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -700,4 +866,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("threads") = 1024);
     m.def("rollout_tail_bounds", &rollout_tail_bounds,
           "(max receiver rows, max nodes) the single-workgroup tail takes");
+    m.def("edge_inputs_bf16", &edge_inputs_bf16,
+          "[x[dst], x[src], edge_attr] as zero-padded bf16 rows",
+          py::arg("x"), py::arg("edge_index"), py::arg("edge_attr"),
+          py::arg("rows_padded"));
+    m.def("attn_aggregate_gamma_in", &attn_aggregate_gamma_in,
+          "segment attention sum ++ x as zero-padded bf16 rows",
+          py::arg("msg"), py::arg("gate"), py::arg("seg"), py::arg("x"),
+          py::arg("n_rows"), py::arg("num_nodes"), py::arg("rows_padded"));
+    m.def("rows_cat_pad_bf16", &rows_cat_pad_bf16,
+          "[a_bf16, b_fp32] as zero-padded bf16 rows",
+          py::arg("a"), py::arg("b"), py::arg("n_rows"),
+          py::arg("rows_padded"));
+    m.def("mirror_table", &mirror_table,
+          "checked host table (n, 8) int64 for refresh_mirrors");
+    m.def("refresh_mirrors", &refresh_mirrors,
+          "refresh every bf16 weight/bias mirror of a table in one launch",
+          py::arg("table"), py::arg("max_groups"));
 }

@@ -15,31 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <cfloat>
 
-#define BLOCK 256
-#define WAVE 64
+#include "segops_common.h"
 
-__device__ __forceinline__ float wave_reduce_sum(float v) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        v += __shfl_down(v, off, WAVE);
-    return v;
-}
-
-__device__ __forceinline__ float wave_reduce_max(float v) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        v = fmaxf(v, __shfl_down(v, off, WAVE));
-    return v;
-}
-
-__device__ __forceinline__ float block_reduce_sum(float v, float* red,
-                                                  int wid, int lane) {
-    v = wave_reduce_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
+#define BLOCK SEG_BLOCK
+#define WAVE SEG_WAVE
 
 // ---------------------------------------------------------------- forward
 extern "C" __global__ void seg_attn_fwd(
@@ -51,63 +30,10 @@ extern "C" __global__ void seg_attn_fwd(
         int N, int D) {
     const int n = blockIdx.x;
     if (n >= N) return;
-    const int lo = ptr[n], hi = ptr[n + 1];
-    const int deg = hi - lo;
-    const int tid = threadIdx.x;
-    const int wid = tid / WAVE, lane = tid % WAVE;
-
     __shared__ __attribute__((aligned(16))) float red[4];
-
-    float* out_row = out + (size_t)n * D;
-    if (deg == 0) {
-        for (int d = tid; d < D; d += BLOCK) out_row[d] = 0.f;
-        return;
-    }
-
-    // 1) segment max of gate
-    float m = -FLT_MAX;
-    for (int e = tid; e < deg; e += BLOCK) m = fmaxf(m, gate[lo + e]);
-    m = wave_reduce_max(m);
-    if (lane == 0) red[wid] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-
-    // 2) exp, stage into att, segment sum
-    float s = 0.f;
-    for (int e = tid; e < deg; e += BLOCK) {
-        const float x = __expf(gate[lo + e] - m);
-        att[lo + e] = x;
-        s += x;
-    }
-    s = block_reduce_sum(s, red, wid, lane);
-    const float inv = 1.f / (s + 1e-16f);
-
-    // 3) normalize in place
-    for (int e = tid; e < deg; e += BLOCK) att[lo + e] *= inv;
-    __syncthreads();
-
-    // 4) out[n][:] = sum_e att[e] * msg[e][:]  (lanes own feature columns)
-    if ((D & 3) == 0) {
-        const int D4 = D >> 2;
-        for (int d4 = tid; d4 < D4; d4 += BLOCK) {
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int e = 0; e < deg; ++e) {
-                const float w = att[lo + e];
-                const float4 v = reinterpret_cast<const float4*>(
-                    msg + (size_t)(lo + e) * D)[d4];
-                acc.x += w * v.x; acc.y += w * v.y;
-                acc.z += w * v.z; acc.w += w * v.w;
-            }
-            reinterpret_cast<float4*>(out_row)[d4] = acc;
-        }
-    } else {
-        for (int d = tid; d < D; d += BLOCK) {
-            float acc = 0.f;
-            for (int e = 0; e < deg; ++e)
-                acc += att[lo + e] * msg[(size_t)(lo + e) * D + d];
-            out_row[d] = acc;
-        }
-    }
+    // body shared with mlp_glue.hip (segops_common.h)
+    seg_attn_row(msg, gate, ptr[n], ptr[n + 1], att, out + (size_t)n * D, D,
+                 red);
 }
 
 // ---------------------------------------------------------------- backward

@@ -128,6 +128,11 @@ class RolloutEngine:
                       and self.N <= TAIL_MAX_NODES
                       and ops.rollout_tail_supported(self.n_rec, self.N))
 
+        # padded-bf16 actor chain (mlp_glue.hip) in the policy graphs;
+        # GCBF_AMD_ACTOR_GLUE=0 keeps the eager composition (read here, as
+        # the tail switch is)
+        self._glue = os.environ.get("GCBF_AMD_ACTOR_GLUE", "1") != "0"
+
         self._load_graph_from_env()
         self._capture()
         # attach the ring store up front so per-step snapshots can be
@@ -147,6 +152,7 @@ class RolloutEngine:
                           u_ref=self.u_ref[i])
         data.seg_dst = self.seg[i]
         data.agents_first_n = self.n if self.agent_mask is not None else None
+        data.actor_glue = self._glue
         with torch.no_grad():
             if explore:
                 # exploration step: the action is zeroed (pure nominal
