@@ -173,10 +173,35 @@ class CBFGNN(nn.Module):
             nm = data.agent_index      # static LONG indices (capture-safe)
         elif data.agents_first_n is not None:
             nm = data.agents_first_n
-        x = self.feat_transformer.module_0(
-            data.x, data.edge_attr, data.edge_index,
-            node_mask=nm, seg_dst=data.seg_dst)
+        layer = self.feat_transformer.module_0
+        if data.update_glue and self._update_glue_applies(data, nm):
+            # the update's padded-bf16 chain: the same GEMMs on the same
+            # operand values, glue kernels between them, either grad mode
+            # (tests/test_update_glue.py).  γ's pad rows reach feat_2_CBF
+            # unzeroed: GEMM rows are independent, and the slice's backward
+            # supplies the zero pad-row gradient the chain needs.
+            from ..nn import fused
+            from ..nn.gnn import _glue_rows
+            feat = layer.forward_padded_bf16_train(
+                data.x, data.edge_attr, data.edge_index, nm, data.seg_dst)
+            out = fused.run_plan_padded_bf16_train(self.feat_2_CBF._plan,
+                                                   feat)
+            return out[:_glue_rows(data.x, nm)[0]].float()
+        x = layer(data.x, data.edge_attr, data.edge_index,
+                  node_mask=nm, seg_dst=data.seg_dst)
         return self.feat_2_CBF(x)
+
+    def _update_glue_applies(self, data: GraphBatch, nm) -> bool:
+        from ..nn import fused
+        from ..nn.gnn import _glue_rows
+        rows = _glue_rows(data.x, nm)
+        f2c = self.feat_2_CBF
+        return (rows is not None
+                and self.feat_transformer.module_0.update_glue_applies(
+                    data.x, data.edge_attr, data.edge_index, nm)
+                and f2c.fused_mfma
+                and fused.plan_on_library(
+                    f2c._plan, -(-rows[0] // f2c.BUCKET) * f2c.BUCKET))
 
     def attention(self, data: GraphBatch) -> Tensor:
         return self.feat_transformer.module_0.attention(data)
@@ -228,6 +253,13 @@ class GCBF(Algorithm):
 
         # DP hook: called after backward, before the optimizer steps
         self.grad_sync: Optional[Callable[[], None]] = None
+
+        # eager inner iterations run the networks' padded-bf16 glue chain
+        # (ops/hip/mlp_glue.hip); 0 keeps the plain forwards.  Read once
+        # here and carried on the batches _iter_eager creates.
+        self._update_glue = (
+            os.environ.get("GCBF_AMD_UPDATE_GLUE", "1") != "0")
+        self._agent_index_cache = {}
 
         # device ring of replayed states (fast batched re-batching for the
         # eager update path; also backs the captured update engine)
@@ -336,6 +368,37 @@ class GCBF(Algorithm):
                 max(1, self.batch_size // 5), seg_len)
         return graph_list
 
+    def _stamp_glue(self, g: GraphBatch, from_ring: bool = True
+                    ) -> GraphBatch:
+        """Carry the update-glue switch on a batch ``_iter_eager`` made.  A
+        uniform batch with obstacle rows also gets its static agent-row
+        index (agents are the first rows of every graph), which the glue
+        needs in place of the boolean mask.  Side effect outside the
+        networks: with ``agent_index`` set, ``env.forward_graph`` and the
+        dynamics take their integer-index branch (``index_select`` /
+        ``index_copy``) where they took the boolean-mask one, as they do for
+        the captured update engine's batches; same values and gradients.
+        Ring batches only: every graph of a ring has ``ring.N`` nodes with
+        its ``ring.n`` agents first.  GCBF itself only, subclasses keep the
+        plain forwards."""
+        if type(self) is not GCBF or not self._update_glue \
+                or not g.x.is_cuda \
+                or getattr(self._env, "_max_neighbors", None) is not None:
+            return g
+        g.update_glue = True
+        if g.agent_mask is not None and g.agent_index is None \
+                and from_ring and self._ring is not None \
+                and g.num_nodes % self._ring.N == 0:
+            L = g.num_nodes // self._ring.N
+            ai = self._agent_index_cache.get(L)
+            if ai is None:
+                dev = g.x.device
+                ai = (torch.arange(L, device=dev).unsqueeze(1) * self._ring.N
+                      + torch.arange(self._ring.n, device=dev)).reshape(-1)
+                self._agent_index_cache[L] = ai
+            g.agent_index = ai
+        return g
+
     def _zero_grad(self):
         self.optim_cbf.zero_grad(set_to_none=True)
         self.optim_actor.zero_grad(set_to_none=True)
@@ -404,9 +467,11 @@ class GCBF(Algorithm):
                 import warnings
                 warnings.warn("ring batch failed; falling back to from_list")
                 self._ring = None
+        from_ring = graphs is not None
         if graphs is None:
             graphs = GraphBatch.from_list(graph_list)
         graphs.edge_attr.requires_grad_(True)
+        self._stamp_glue(graphs, from_ring)
         prof.lap("batch")
         # σ reuse ends before backward: the optimizer step changes the weights
         with sn_weight_reuse():
@@ -417,7 +482,8 @@ class GCBF(Algorithm):
                 # calls (gcbf/algo/gcbf.py:161,194) and evaluates both sides
                 # of the finite difference under the SAME spectral-norm σ
                 graphs_next = self._env.forward_graph(graphs, actions)
-                both = GraphBatch.from_list([graphs, graphs_next])
+                both = self._stamp_glue(
+                    GraphBatch.from_list([graphs, graphs_next]), from_ring)
                 h_both = self.cbf(both)
                 n_ag = h_both.shape[0] // 2
                 h, h_next = h_both[:n_ag], h_both[n_ag:]
@@ -433,8 +499,9 @@ class GCBF(Algorithm):
             # fixed-topology path.
             with trace_range("gcbf/h_dot"):
                 with torch.no_grad():
-                    relinked = self._env.add_communication_links_batched(
-                        graphs_next.detach())
+                    relinked = self._stamp_glue(
+                        self._env.add_communication_links_batched(
+                            graphs_next.detach()), from_ring)
                     h_next_new_link = self.cbf(relinked)
         prof.lap("hdot")
 

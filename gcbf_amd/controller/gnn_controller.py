@@ -43,6 +43,8 @@ class GNNController(MultiAgentController):
             nm = data.agent_index      # static LONG indices (capture-safe)
         elif data.agents_first_n is not None:
             nm = data.agents_first_n
+        if data.update_glue and self._update_glue_applies(data, nm):
+            return self._forward_update_glue(data, nm)
         if self._glue_applies(data, nm):
             return self._forward_glue(data, nm)
         x = self.feat_transformer.module_0(
@@ -91,4 +93,39 @@ class GNNController(MultiAgentController):
         out = fused.run_plan_padded_bf16(
             self.feat_2_action._plan,
             ops.rows_cat_pad_bf16(feat, data.u_ref, n_rows, feat.shape[0]))
+        return out[:n_rows].float()
+
+    # ---------------------------------------------- update glue path
+    def _update_glue_applies(self, data: GraphBatch, nm) -> bool:
+        """The update's padded-bf16 chain (either grad mode) serves GPU
+        batches with a static agent-row layout on the library-GEMM plans;
+        ``data.update_glue`` carries GCBF's switch."""
+        from ..nn import fused
+        from ..nn.gnn import _glue_rows
+        rows = _glue_rows(data.x, nm)
+        f2a = self.feat_2_action
+        return (rows is not None and data.u_ref is not None
+                and data.u_ref.dtype == torch.float32
+                and data.u_ref.shape[0] == rows[0]
+                and not data.u_ref.requires_grad
+                and self.feat_transformer.module_0.update_glue_applies(
+                    data.x, data.edge_attr, data.edge_index, nm)
+                and f2a.fused_mfma
+                and fused.plan_on_library(
+                    f2a._plan, -(-rows[0] // f2a.BUCKET) * f2a.BUCKET))
+
+    def _forward_update_glue(self, data: GraphBatch, nm) -> Tensor:
+        """:meth:`forward`'s GEMMs on the same operand values, differentiable,
+        with glue kernels between them (tests/test_update_glue.py)."""
+        from .. import ops
+        from ..nn import fused
+        from ..nn.gnn import _glue_rows
+        n_rows = _glue_rows(data.x, nm)[0]
+        feat = self.feat_transformer.module_0.forward_padded_bf16_train(
+            data.x, data.edge_attr, data.edge_index, nm, data.seg_dst)
+        out = fused.run_plan_padded_bf16_train(
+            self.feat_2_action._plan,
+            ops.rows_cat_pad_bf16_grad(feat, data.u_ref, n_rows,
+                                       feat.shape[0]))
+        # the slice's backward supplies the zero pad rows the chain needs
         return out[:n_rows].float()

@@ -44,7 +44,8 @@ class GraphBatch:
 
     __slots__ = ("x", "pos", "states", "edge_index", "edge_attr", "agent_mask",
                  "u_ref", "_ptr", "_dst_ptr", "seg_dst", "agents_first_n",
-                 "ring_id", "agent_index", "_edge_count", "actor_glue")
+                 "ring_id", "agent_index", "_edge_count", "actor_glue",
+                 "update_glue")
 
     def __init__(
             self,
@@ -87,6 +88,10 @@ class GraphBatch:
         # optional: caller's switch for the actor's padded-bf16 glue path
         # (True/False; None lets the controller read GCBF_AMD_ACTOR_GLUE)
         self.actor_glue = None
+        # optional: True where the update's eager iteration wants the
+        # networks' padded-bf16 chain in either grad mode (GCBF reads
+        # GCBF_AMD_UPDATE_GLUE when it is built); None/False: plain forward
+        self.update_glue = None
 
     # ------------------------------------------------------------------ sizes
     @property

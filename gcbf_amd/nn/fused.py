@@ -289,6 +289,60 @@ def run_plan_padded_bf16(plan, h: Tensor) -> Tensor:
     return h
 
 
+def plan_on_library(plan, rows_padded: int) -> bool:
+    """True where :func:`run_plan_padded_bf16_train` applies: at this row
+    count :func:`run_plan` sends every layer, plain or spectral-normed, to
+    the library GEMM.  Spectral-normed layers get their bf16 operands from
+    autocast, so a plan with one needs bf16 autocast to be on."""
+    from .mlp import SNLinear
+    sn = any(isinstance(lin, SNLinear) for lin, _ in plan)
+    if sn and not (torch.is_autocast_enabled()
+                   and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+        return False
+    return all(isinstance(lin, (torch.nn.Linear, SNLinear))
+               and lin.bias is not None
+               and not shapes_ok(rows_padded, lin.weight_orig.shape[0]
+                                 if isinstance(lin, SNLinear)
+                                 else lin.weight.shape[0])
+               for lin, _ in plan)
+
+
+def run_plan_padded_bf16_train(plan, h: Tensor) -> Tensor:
+    """:func:`run_plan_padded_bf16` for the update: differentiable, and
+    spectral-normed layers allowed.  Per layer the GEMM :func:`run_plan`
+    issues on the library path in the current grad mode, on the same
+    operand values: in grad mode ``F.linear`` on per-call bf16 casts of the
+    master weight and bias, without it on the mirrors; for a spectral-normed
+    layer ``F.linear`` on the (cached) ``effective_weight()`` under the
+    caller's autocast.  What is dropped is the pad ``cat`` and cast on
+    entry, the cast and row slice on exit, and the spectral-norm branch's
+    ``h.float()``, which autocast casts straight back.
+
+    The caller owes every padded output a gradient that is exactly zero on
+    pad rows (the row slice's backward supplied those zeros): bias and
+    weight gradients then sum the same addends as before."""
+    from .mlp import SNLinear
+    grad_mode = torch.is_grad_enabled()
+    for lin, act in plan:
+        if isinstance(lin, SNLinear):
+            h = F.linear(h, lin.effective_weight(), lin.bias)
+        elif grad_mode:
+            h = F.linear(h, lin.weight.bfloat16(), lin.bias.bfloat16())
+        else:
+            wb, bb, _ = _mirror(lin)
+            h = F.linear(h, wb[:, :lin.weight.shape[1]], bb)
+        h = _apply_act(h, act)
+    return h
+
+
+def plan_params(plan) -> list:
+    """The parameters a plan's layers read (plain layers with a bias only,
+    see :func:`plan_is_plain`)."""
+    assert all(isinstance(lin, torch.nn.Linear) and lin.bias is not None
+               for lin, _ in plan), "plan_params: plain biased layers only"
+    return [p for lin, _ in plan for p in (lin.weight, lin.bias)]
+
+
 def _weight_of(lin) -> Tensor:
     from .mlp import SNLinear
     if isinstance(lin, SNLinear):

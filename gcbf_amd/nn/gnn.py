@@ -52,7 +52,73 @@ def _gather_edge_inputs(x: Tensor, edge_attr: Tensor,
                       edge_attr], dim=1)
 
 
-class CBFGNNLayer(nn.Module):
+def _glue_rows(x: Tensor, node_mask):
+    """(row count, row-index tensor or None) of a static agent-row layout:
+    every node (``None``), the first n (``int``) or a LONG index tensor.  A
+    boolean mask has no static layout: ``None``."""
+    if node_mask is None:
+        return x.shape[0], None
+    if isinstance(node_mask, int):
+        return node_mask, None
+    if node_mask.dtype == torch.long and node_mask.dim() == 1:
+        return node_mask.shape[0], node_mask
+    return None
+
+
+class _UpdateGlueMixin:
+    """Padded-bf16 chain of an attention layer in either grad mode (the
+    update's forwards): the GEMMs :meth:`forward` issues, on the same
+    operand values, with the movement between them done by the glue kernels
+    and their backwards (ops/hip/mlp_glue.hip)."""
+
+    def update_glue_applies(self, x: Tensor, edge_attr: Tensor,
+                            edge_index: Tensor, node_mask) -> bool:
+        from . import fused
+        rows = _glue_rows(x, node_mask)
+        if rows is None or not x.is_cuda or not ops.hip_available():
+            return False
+        n_rows, _ = rows
+        E = edge_index.shape[1]
+        bucket = MLP.BUCKET
+        gate = self.aggr_module.gate_nn
+        return (n_rows > 0 and E > 0 and not x.requires_grad
+                and x.dtype == torch.float32
+                and edge_attr.dtype == torch.float32
+                and fused.plan_is_plain(gate._plan, -(-E // bucket) * bucket)
+                and all(lin.bias is not None for lin, _ in gate._plan)
+                and all(m.fused_mfma and fused.plan_on_library(
+                            m._plan, -(-r // bucket) * bucket)
+                        for m, r in ((self.phi, E), (self.gamma, n_rows),
+                                     (gate, E))))
+
+    def forward_padded_bf16_train(self, x: Tensor, edge_attr: Tensor,
+                                  edge_index: Tensor, node_mask,
+                                  seg_dst: Optional[Tensor] = None) -> Tensor:
+        """γ's output for the rows ``node_mask`` selects, as bf16 rows
+        padded to the GEMM bucket.  The caller owes it a gradient that is
+        zero on pad rows."""
+        from . import fused
+        from .mlp import SNLinear
+        bucket = MLP.BUCKET
+        n_rows, idx = _glue_rows(x, node_mask)
+        rows_e = -(-edge_index.shape[1] // bucket) * bucket
+        rows_n = -(-n_rows // bucket) * bucket
+        msg = fused.run_plan_padded_bf16_train(
+            self.phi._plan,
+            ops.edge_inputs_bf16_grad(x, edge_index, edge_attr, rows_e))
+        gate_plan = self.aggr_module.gate_nn._plan
+        gamma_in = ops.gate_attn_gamma_in(
+            msg, lambda m: fused.run_plan_padded_bf16_train(gate_plan, m),
+            fused.plan_params(gate_plan), x,
+            edge_index[1] if seg_dst is None else seg_dst, idx, n_rows,
+            x.shape[0], rows_n,
+            # φ ending in a spectral-normed layer hands the eager path a
+            # bf16 msg, whose two gradients meet in bf16
+            round_prod=isinstance(self.phi._plan[-1][0], SNLinear))
+        return fused.run_plan_padded_bf16_train(self.gamma._plan, gamma_in)
+
+
+class CBFGNNLayer(_UpdateGlueMixin, nn.Module):
     """Attention message-passing layer of the CBF GNN.
 
     Reference: gcbf/nn/gnn.py:14-53.  φ and γ are spectral-normed
@@ -96,7 +162,7 @@ class CBFGNNLayer(nn.Module):
         return ops.segment_softmax(gate, data.edge_index[1], data.num_nodes)
 
 
-class ControllerGNNLayer(nn.Module):
+class ControllerGNNLayer(_UpdateGlueMixin, nn.Module):
     """Same structure as CBFGNNLayer without spectral norm (reference
     gcbf/nn/gnn.py:56-79)."""
 

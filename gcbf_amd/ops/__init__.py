@@ -423,6 +423,142 @@ def rows_cat_pad_bf16(a: Tensor, b: Tensor, n_rows: int,
 
 
 # --------------------------------------------------------------------------
+# update glue: the same kernels in grad mode, with their backwards.  GPU and
+# extension only (callers check ``hip_available``); every backward hands its
+# padded bf16 input a gradient that is exactly zero on pad rows.
+# --------------------------------------------------------------------------
+
+class _EdgeInputsBf16(torch.autograd.Function):
+    """:func:`edge_inputs_bf16` with the gradient of ``edge_attr``:
+    ``d_edge_attr[e] = float(dIn[e, 2*node_dim:])``, what the cast, the row
+    slice and the cat of the eager composition hand back.  ``x`` takes no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, edge_index: Tensor, edge_attr: Tensor,
+                rows_padded: int):
+        ctx.dims = (edge_attr.shape[0], x.shape[1], edge_attr.shape[1])
+        return _require_ext("edge_inputs_bf16").edge_inputs_bf16(
+            x.contiguous(), edge_index.contiguous(), edge_attr.contiguous(),
+            rows_padded)
+
+    @staticmethod
+    def backward(ctx, d_in: Tensor):
+        E, nd, ed = ctx.dims
+        return None, None, _EXT.edge_inputs_bwd(d_in.contiguous(), E, nd,
+                                                ed), None
+
+
+def edge_inputs_bf16_grad(x: Tensor, edge_index: Tensor, edge_attr: Tensor,
+                          rows_padded: int) -> Tensor:
+    return _EdgeInputsBf16.apply(x, edge_index, edge_attr, rows_padded)
+
+
+class _GateAttnGammaIn(torch.autograd.Function):
+    """Gate MLP + segment attention + γ input as ONE autograd node.
+
+    ``msg`` (padded bf16, φ's output) feeds both the gate MLP and the
+    weighted sum.  Eagerly the two gradients meet in fp32 at φ's fp32
+    output and are rounded to bf16 once; as two nodes on a bf16 tensor
+    they would be rounded twice.  So the gate MLP runs here on a detached
+    copy with a graph of its own, and backward is: gate gradient (kernel)
+    -> that graph's backward (the same GEMMs autograd would run) -> message
+    gradient ``bf16(att * g + float(dmsg_gate))`` (kernel).  ``round_prod``
+    is for a φ whose eager output was bf16 already (spectral-normed last
+    layer): there ``att * g`` was rounded to bf16 before the sum.
+    ``params`` are the leaves ``gate_fn`` reads; their gradients are
+    returned through this node.  The inner graph is used up by the first
+    backward: one backward per forward, no double backward."""
+
+    @staticmethod
+    def forward(ctx, msg: Tensor, gate_fn, x: Tensor, seg: Tensor, idx,
+                n_rows: int, num_nodes: int, rows_padded: int,
+                round_prod: bool, *params):
+        ext = _require_ext("attn_gamma_in")
+        with torch.enable_grad():
+            msg_in = msg.detach().requires_grad_(True)
+            gate = gate_fn(msg_in)
+        out, att = ext.attn_gamma_in_fwd(
+            msg, gate.detach().reshape(-1), seg.contiguous(), x.contiguous(),
+            idx, n_rows, num_nodes, rows_padded)
+        ctx.save_for_backward(msg, att, seg, *params)
+        ctx.idx = idx
+        ctx.inner = (msg_in, gate)
+        ctx.dims = (n_rows, num_nodes, round_prod)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out: Tensor):
+        msg, att, seg, *params = ctx.saved_tensors
+        if ctx.inner is None:
+            raise RuntimeError(
+                "gate_attn_gamma_in supports one backward per forward: the "
+                "gate MLP's graph was freed by the first one")
+        msg_in, gate = ctx.inner
+        ctx.inner = None
+        n_rows, num_nodes, round_prod = ctx.dims
+        d_out = d_out.contiguous()
+        seg = seg.contiguous()
+        dgate = _EXT.attn_gamma_in_bwd_gate(d_out, msg, att, seg, ctx.idx,
+                                            n_rows, num_nodes)
+        wanted = [p for p, need in zip(params, ctx.needs_input_grad[9:])
+                  if need]
+        grads = torch.autograd.grad(gate, [msg_in] + wanted, dgate)
+        dmsg = _EXT.attn_gamma_in_bwd_msg(d_out, att, seg, ctx.idx,
+                                          grads[0].contiguous(), n_rows,
+                                          num_nodes, round_prod)
+        it = iter(grads[1:])
+        dparams = [next(it) if need else None
+                   for need in ctx.needs_input_grad[9:]]
+        return (dmsg, None, None, None, None, None, None, None, None,
+                *dparams)
+
+
+def gate_attn_gamma_in(msg: Tensor, gate_fn, params, x: Tensor, seg: Tensor,
+                       idx: Optional[Tensor], n_rows: int, num_nodes: int,
+                       rows_padded: int, round_prod: bool = False) -> Tensor:
+    """bf16 (rows_padded, D+node_dim) γ input from φ's padded bf16 output:
+    ``gate = gate_fn(msg)`` (padded bf16 in and out), softmax over the edges
+    of each node, weighted message sum, ``x`` appended.  Row r is node
+    ``idx[r]`` (strictly increasing int64), or node r without ``idx``.  In
+    grad mode one autograd node (see :class:`_GateAttnGammaIn`)."""
+    if torch.is_grad_enabled() and (msg.requires_grad or any(
+            p.requires_grad for p in params)):
+        return _GateAttnGammaIn.apply(msg, gate_fn, x, seg, idx, n_rows,
+                                      num_nodes, rows_padded, round_prod,
+                                      *params)
+    gate = gate_fn(msg)
+    return _require_ext("attn_gamma_in").attn_gamma_in_fwd(
+        msg.contiguous(), gate.reshape(-1).contiguous(), seg.contiguous(),
+        x.contiguous(), idx, n_rows, num_nodes, rows_padded)[0]
+
+
+class _RowsCatPadBf16(torch.autograd.Function):
+    """:func:`rows_cat_pad_bf16` with the gradient of ``a`` (itself
+    ``rows_padded`` rows): the first ``Da`` columns of the real rows, zero
+    pad rows.  ``b`` takes none."""
+
+    @staticmethod
+    def forward(ctx, a: Tensor, b: Tensor, n_rows: int, rows_padded: int):
+        assert a.shape[0] == rows_padded, "a must already be row-padded"
+        ctx.dims = (a.shape[1], n_rows)
+        return _require_ext("rows_cat_pad_bf16").rows_cat_pad_bf16(
+            a.contiguous(), b.contiguous(), n_rows, rows_padded)
+
+    @staticmethod
+    def backward(ctx, d_in: Tensor):
+        Da, n_rows = ctx.dims
+        return _EXT.rows_cat_bwd(d_in.contiguous(), Da, n_rows), None, None, \
+            None
+
+
+def rows_cat_pad_bf16_grad(a: Tensor, b: Tensor, n_rows: int,
+                           rows_padded: int) -> Tensor:
+    return _RowsCatPadBf16.apply(a, b, n_rows, rows_padded)
+
+
+# --------------------------------------------------------------------------
 # episode reset
 # --------------------------------------------------------------------------
 

@@ -104,9 +104,23 @@ extern "C" void launch_edge_inputs_bf16(const float* x, const long* ei,
                                         hipStream_t stream);
 extern "C" void launch_attn_gamma_in(const void* msg, const void* gate,
                                      int gate_is_bf16, const long* seg,
-                                     const float* x, float* att, void* out,
-                                     int E, int D, int nd, int n_rows,
+                                     const float* x, const long* idx,
+                                     float* att, void* out, int E, int D,
+                                     int nd, int n_rows, int num_nodes,
                                      int rows, hipStream_t stream);
+extern "C" void launch_edge_inputs_bwd(const void* din, float* dea, int nd,
+                                       int ed, long E, hipStream_t stream);
+extern "C" void launch_attn_gamma_in_bwd_gate(
+        const void* dout, const void* msg, const float* att, const long* seg,
+        const long* idx, float* stage, void* dgate, int E, int D, int nd,
+        int n_rows, int num_nodes, int rows, hipStream_t stream);
+extern "C" void launch_attn_gamma_in_bwd_msg(
+        const void* dout, const float* att, const long* seg, const long* idx,
+        const void* dmsg_gate, void* dmsg, int E, int D, int nd, int n_rows,
+        int num_nodes, int rows, int round_prod, hipStream_t stream);
+extern "C" void launch_rows_cat_bwd(const void* din, void* da, int Da, int Db,
+                                    long n_rows, long rows,
+                                    hipStream_t stream);
 extern "C" void launch_rows_cat_pad_bf16(const void* a, const float* b,
                                          void* out, int Da, int Db,
                                          long n_rows, long rows,
@@ -678,10 +692,13 @@ torch::Tensor edge_inputs_bf16(torch::Tensor x, torch::Tensor edge_index,
     return out;
 }
 
-torch::Tensor attn_aggregate_gamma_in(torch::Tensor msg, torch::Tensor gate,
-                                      torch::Tensor seg, torch::Tensor x,
-                                      int64_t n_rows, int64_t num_nodes,
-                                      int64_t rows_padded) {
+// out (rows_padded, D+nd) bf16 and the normalised attention weights att (E,)
+// fp32.  Row r aggregates node idx[r] (int64, strictly increasing), or node
+// r without an index.  att is written on the edges of those nodes only.
+std::vector<torch::Tensor> attn_gamma_in_fwd(
+        torch::Tensor msg, torch::Tensor gate, torch::Tensor seg,
+        torch::Tensor x, c10::optional<torch::Tensor> idx, int64_t n_rows,
+        int64_t num_nodes, int64_t rows_padded) {
     CHECK_IN(msg); CHECK_IN(gate); CHECK_IN(seg); CHECK_IN(x);
     TORCH_CHECK(msg.scalar_type() == torch::kBFloat16 && msg.dim() == 2,
                 "msg must be bf16 (rows, D)");
@@ -695,10 +712,19 @@ torch::Tensor attn_aggregate_gamma_in(torch::Tensor msg, torch::Tensor gate,
     const int64_t E = seg.size(0), D = msg.size(1), nd = x.size(1);
     TORCH_CHECK(msg.size(0) >= E && gate.numel() >= E,
                 "msg and gate must cover every edge slot");
-    TORCH_CHECK(n_rows >= 0 && n_rows <= num_nodes && n_rows <= x.size(0) &&
-                n_rows <= rows_padded,
+    TORCH_CHECK(n_rows >= 0 && n_rows <= num_nodes &&
+                num_nodes <= x.size(0) && n_rows <= rows_padded,
                 "attn_aggregate_gamma_in: bad n_rows ", n_rows);
+    const int64_t* iptr = nullptr;
+    if (idx.has_value()) {
+        CHECK_IN(idx.value());
+        TORCH_CHECK(idx->scalar_type() == torch::kInt64 && idx->dim() == 1 &&
+                    idx->size(0) == n_rows,
+                    "idx must be int64 (n_rows,)");
+        iptr = idx->data_ptr<int64_t>();
+    }
     TORCH_CHECK(E < (int64_t(1) << 31) && rows_padded < (int64_t(1) << 31) &&
+                num_nodes < (int64_t(1) << 31) &&
                 E * D < (int64_t(1) << 40) && D + nd < (int64_t(1) << 24),
                 "attn_aggregate_gamma_in: sizes out of range");
     auto out = torch::empty({rows_padded, D + nd}, msg.options());
@@ -708,10 +734,134 @@ torch::Tensor attn_aggregate_gamma_in(torch::Tensor msg, torch::Tensor gate,
         launch_attn_gamma_in(msg.data_ptr(), gate.data_ptr(),
                              gate.scalar_type() == torch::kBFloat16 ? 1 : 0,
                              seg.data_ptr<int64_t>(), x.data_ptr<float>(),
-                             att.data_ptr<float>(), out.data_ptr(), (int)E,
-                             (int)D, (int)nd, (int)n_rows, (int)rows_padded,
+                             iptr, att.data_ptr<float>(), out.data_ptr(),
+                             (int)E, (int)D, (int)nd, (int)n_rows,
+                             (int)num_nodes, (int)rows_padded,
                              current_stream());
-    return out;
+    return {out, att};
+}
+
+torch::Tensor attn_aggregate_gamma_in(torch::Tensor msg, torch::Tensor gate,
+                                      torch::Tensor seg, torch::Tensor x,
+                                      int64_t n_rows, int64_t num_nodes,
+                                      int64_t rows_padded) {
+    return attn_gamma_in_fwd(msg, gate, seg, x, c10::nullopt, n_rows,
+                             num_nodes, rows_padded)[0];
+}
+
+// shared checks of the two backward launches; returns the idx pointer
+static const int64_t* attn_bwd_checks(
+        const torch::Tensor& dout, const torch::Tensor& att,
+        const torch::Tensor& seg, const c10::optional<torch::Tensor>& idx,
+        int64_t n_rows, int64_t num_nodes, int64_t D, int64_t rows) {
+    CHECK_IN(dout); CHECK_IN(att); CHECK_IN(seg);
+    TORCH_CHECK(dout.scalar_type() == torch::kBFloat16 && dout.dim() == 2 &&
+                dout.size(1) >= D && dout.size(0) >= n_rows,
+                "dout must be bf16 (>= n_rows, D + nd)");
+    TORCH_CHECK(seg.scalar_type() == torch::kInt64 && seg.dim() == 1,
+                "seg must be int64 (E,)");
+    const int64_t E = seg.size(0);
+    TORCH_CHECK(att.scalar_type() == torch::kFloat32 && att.numel() == E,
+                "att must be fp32 (E,)");
+    TORCH_CHECK(n_rows >= 1 && n_rows <= num_nodes && rows >= E,
+                "attn_gamma_in_bwd: bad n_rows / rows");
+    TORCH_CHECK(rows < (int64_t(1) << 31) && num_nodes < (int64_t(1) << 31) &&
+                rows * D < (int64_t(1) << 40) &&
+                dout.size(1) < (int64_t(1) << 24),
+                "attn_gamma_in_bwd: sizes out of range");
+    if (!idx.has_value()) return nullptr;
+    CHECK_IN(idx.value());
+    TORCH_CHECK(idx->scalar_type() == torch::kInt64 && idx->dim() == 1 &&
+                idx->size(0) == n_rows, "idx must be int64 (n_rows,)");
+    return idx->data_ptr<int64_t>();
+}
+
+// the caller's output buffer where one is given (tests prefill it), else a
+// fresh one; every kernel that takes it writes every element
+static torch::Tensor glue_out(const c10::optional<torch::Tensor>& out,
+                              torch::IntArrayRef sizes,
+                              const torch::TensorOptions& opts) {
+    if (!out.has_value()) return torch::empty(sizes, opts);
+    CHECK_IN(out.value());
+    TORCH_CHECK(out->sizes() == sizes &&
+                out->scalar_type() == opts.dtype().toScalarType(),
+                "out has shape ", out->sizes(), ", expected ", sizes);
+    return *out;
+}
+
+// dgate (rows, 1) bf16 for the gate MLP's output; rows = msg.size(0)
+torch::Tensor attn_gamma_in_bwd_gate(
+        torch::Tensor dout, torch::Tensor msg, torch::Tensor att,
+        torch::Tensor seg, c10::optional<torch::Tensor> idx, int64_t n_rows,
+        int64_t num_nodes, c10::optional<torch::Tensor> out = c10::nullopt) {
+    CHECK_IN(msg);
+    TORCH_CHECK(msg.scalar_type() == torch::kBFloat16 && msg.dim() == 2,
+                "msg must be bf16 (rows, D)");
+    const int64_t rows = msg.size(0), D = msg.size(1), E = seg.size(0);
+    const int64_t* iptr = attn_bwd_checks(dout, att, seg, idx, n_rows,
+                                          num_nodes, D, rows);
+    auto dgate = glue_out(out, {rows, 1}, msg.options());
+    auto stage = torch::empty({E}, att.options());
+    launch_attn_gamma_in_bwd_gate(
+        dout.data_ptr(), msg.data_ptr(), att.data_ptr<float>(),
+        seg.data_ptr<int64_t>(), iptr, stage.data_ptr<float>(),
+        dgate.data_ptr(), (int)E, (int)D, (int)(dout.size(1) - D),
+        (int)n_rows, (int)num_nodes, (int)rows, current_stream());
+    return dgate;
+}
+
+// dmsg (rows, D) bf16 for phi's output; dmsg_gate is the gate MLP's
+// gradient for the same tensor.  round_prod: att * g is rounded to bf16
+// before the two are added (a phi whose output was bf16)
+torch::Tensor attn_gamma_in_bwd_msg(
+        torch::Tensor dout, torch::Tensor att, torch::Tensor seg,
+        c10::optional<torch::Tensor> idx, torch::Tensor dmsg_gate,
+        int64_t n_rows, int64_t num_nodes, bool round_prod,
+        c10::optional<torch::Tensor> out = c10::nullopt) {
+    CHECK_IN(dmsg_gate);
+    TORCH_CHECK(dmsg_gate.scalar_type() == torch::kBFloat16 &&
+                dmsg_gate.dim() == 2, "dmsg_gate must be bf16 (rows, D)");
+    const int64_t rows = dmsg_gate.size(0), D = dmsg_gate.size(1);
+    const int64_t* iptr = attn_bwd_checks(dout, att, seg, idx, n_rows,
+                                          num_nodes, D, rows);
+    auto dmsg = glue_out(out, dmsg_gate.sizes(), dmsg_gate.options());
+    TORCH_CHECK(dmsg.data_ptr() != dmsg_gate.data_ptr(),
+                "out must not alias dmsg_gate");
+    launch_attn_gamma_in_bwd_msg(
+        dout.data_ptr(), att.data_ptr<float>(), seg.data_ptr<int64_t>(),
+        iptr, dmsg_gate.data_ptr(), dmsg.data_ptr(), (int)seg.size(0),
+        (int)D, (int)(dout.size(1) - D), (int)n_rows, (int)num_nodes,
+        (int)rows, round_prod ? 1 : 0, current_stream());
+    return dmsg;
+}
+
+torch::Tensor edge_inputs_bwd(torch::Tensor din, int64_t E, int64_t nd,
+                              int64_t ed) {
+    CHECK_IN(din);
+    TORCH_CHECK(din.scalar_type() == torch::kBFloat16 && din.dim() == 2 &&
+                nd >= 0 && ed >= 0 && din.size(1) == 2 * nd + ed &&
+                E >= 0 && din.size(0) >= E,
+                "edge_inputs_bwd: din must be bf16 (>= E, 2*nd+ed)");
+    auto dea = torch::empty({E, ed}, din.options().dtype(torch::kFloat32));
+    if (dea.numel() > 0)
+        launch_edge_inputs_bwd(din.data_ptr(), dea.data_ptr<float>(), (int)nd,
+                               (int)ed, E, current_stream());
+    return dea;
+}
+
+torch::Tensor rows_cat_bwd(torch::Tensor din, int64_t Da, int64_t n_rows,
+                           c10::optional<torch::Tensor> out = c10::nullopt) {
+    CHECK_IN(din);
+    TORCH_CHECK(din.scalar_type() == torch::kBFloat16 && din.dim() == 2 &&
+                Da >= 0 && Da <= din.size(1) && n_rows >= 0 &&
+                n_rows <= din.size(0),
+                "rows_cat_bwd: din must be bf16 (rows, Da+Db)");
+    auto da = glue_out(out, {din.size(0), Da}, din.options());
+    if (da.numel() > 0)
+        launch_rows_cat_bwd(din.data_ptr(), da.data_ptr(), (int)Da,
+                            (int)(din.size(1) - Da), n_rows, din.size(0),
+                            current_stream());
+    return da;
 }
 
 torch::Tensor rows_cat_pad_bf16(torch::Tensor a, torch::Tensor b,
@@ -874,6 +1024,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "segment attention sum ++ x as zero-padded bf16 rows",
           py::arg("msg"), py::arg("gate"), py::arg("seg"), py::arg("x"),
           py::arg("n_rows"), py::arg("num_nodes"), py::arg("rows_padded"));
+    m.def("attn_gamma_in_fwd", &attn_gamma_in_fwd,
+          "attn_aggregate_gamma_in over optional row indices, keeping att",
+          py::arg("msg"), py::arg("gate"), py::arg("seg"), py::arg("x"),
+          py::arg("idx"), py::arg("n_rows"), py::arg("num_nodes"),
+          py::arg("rows_padded"));
+    m.def("attn_gamma_in_bwd_gate", &attn_gamma_in_bwd_gate,
+          "gate gradient of attn_gamma_in_fwd as zero-padded bf16 rows",
+          py::arg("dout"), py::arg("msg"), py::arg("att"), py::arg("seg"),
+          py::arg("idx"), py::arg("n_rows"), py::arg("num_nodes"),
+          py::arg("out") = py::none());
+    m.def("attn_gamma_in_bwd_msg", &attn_gamma_in_bwd_msg,
+          "message gradient of attn_gamma_in_fwd plus the gate MLP's",
+          py::arg("dout"), py::arg("att"), py::arg("seg"), py::arg("idx"),
+          py::arg("dmsg_gate"), py::arg("n_rows"), py::arg("num_nodes"),
+          py::arg("round_prod"), py::arg("out") = py::none());
+    m.def("edge_inputs_bwd", &edge_inputs_bwd,
+          "edge_attr gradient of edge_inputs_bf16 (fp32)",
+          py::arg("din"), py::arg("E"), py::arg("nd"), py::arg("ed"));
+    m.def("rows_cat_bwd", &rows_cat_bwd,
+          "gradient of rows_cat_pad_bf16's bf16 operand, zero pad rows",
+          py::arg("din"), py::arg("Da"), py::arg("n_rows"),
+          py::arg("out") = py::none());
     m.def("rows_cat_pad_bf16", &rows_cat_pad_bf16,
           "[a_bf16, b_fp32] as zero-padded bf16 rows",
           py::arg("a"), py::arg("b"), py::arg("n_rows"),

@@ -50,55 +50,10 @@ extern "C" __global__ void seg_attn_bwd(
         int N, int D) {
     const int n = blockIdx.x;
     if (n >= N) return;
-    const int lo = ptr[n], hi = ptr[n + 1];
-    const int deg = hi - lo;
-    if (deg == 0) return;
-    const int tid = threadIdx.x;
-    const int wid = tid / WAVE, lane = tid % WAVE;
-    const int n_waves = BLOCK / WAVE;
-
     __shared__ __attribute__((aligned(16))) float red[4];
-
-    const float* g = grad_out + (size_t)n * D;
-
-    // pass 1: per-edge dmsg write + dot product (one wave per edge)
-    const bool vec4 = (D & 3) == 0;
-    for (int e = wid; e < deg; e += n_waves) {
-        const float ae = att[lo + e];
-        const float* me = msg + (size_t)(lo + e) * D;
-        float* dme = dmsg + (size_t)(lo + e) * D;
-        float dot = 0.f;
-        if (vec4) {
-            const int D4 = D >> 2;
-            for (int d4 = lane; d4 < D4; d4 += WAVE) {
-                const float4 gv = reinterpret_cast<const float4*>(g)[d4];
-                const float4 mv = reinterpret_cast<const float4*>(me)[d4];
-                float4 dv;
-                dv.x = ae * gv.x; dv.y = ae * gv.y;
-                dv.z = ae * gv.z; dv.w = ae * gv.w;
-                reinterpret_cast<float4*>(dme)[d4] = dv;
-                dot += mv.x * gv.x + mv.y * gv.y + mv.z * gv.z + mv.w * gv.w;
-            }
-        } else {
-            for (int d = lane; d < D; d += WAVE) {
-                const float gv = g[d];
-                dme[d] = ae * gv;
-                dot += me[d] * gv;
-            }
-        }
-        dot = wave_reduce_sum(dot);
-        if (lane == 0) dgate[lo + e] = dot;   // stage s_e
-    }
-    __syncthreads();
-
-    // seg = sum_e att_e * s_e
-    float part = 0.f;
-    for (int e = tid; e < deg; e += BLOCK) part += att[lo + e] * dgate[lo + e];
-    const float seg = block_reduce_sum(part, red, wid, lane);
-
-    // pass 2: dgate (overwrites the staged s_e)
-    for (int e = tid; e < deg; e += BLOCK)
-        dgate[lo + e] = att[lo + e] * (dgate[lo + e] - seg);
+    // body shared with mlp_glue.hip (segops_common.h)
+    seg_attn_bwd_row<true>(grad_out + (size_t)n * D, msg, att, ptr[n],
+                           ptr[n + 1], dmsg, dgate, dgate, D, red);
 }
 
 // ------------------------------------------------------------- launchers

@@ -1,6 +1,7 @@
-// Per-segment body of the CSR attention aggregation, shared by
-// seg_attn_fwd (segops.hip, fp32 in / fp32 out) and attn_gamma_in_kernel
-// (mlp_glue.hip, bf16 messages in / bf16 γ-input row out).  One 256-thread
+// Per-segment bodies of the CSR attention aggregation, shared by
+// seg_attn_fwd / seg_attn_bwd (segops.hip, fp32 in / fp32 out) and the
+// attn_gamma_in kernels (mlp_glue.hip, bf16 messages in / bf16 rows out),
+// forward (seg_attn_row) and backward (seg_attn_bwd_row).  One 256-thread
 // workgroup owns one destination node; the arithmetic is fp32 in one fixed
 // order (max, exp, sum, normalise, weighted sum), so both callers produce
 // the same fp32 accumulators bit for bit.  Loads upcast (exact), the store
@@ -57,6 +58,17 @@ __device__ __forceinline__ void seg_st4(unsigned short* row, int i4,
     row[4 * i4 + 1] = bf16_rne(v.y);
     row[4 * i4 + 2] = bf16_rne(v.z);
     row[4 * i4 + 3] = bf16_rne(v.w);
+}
+
+// like seg_ld4 for a row with no alignment beyond its element type (a bf16
+// row of an odd-width matrix); fp32 rows of D % 4 == 0 are always aligned
+__device__ __forceinline__ float4 seg_ld4_any(const float* row, int i4) {
+    return reinterpret_cast<const float4*>(row)[i4];
+}
+__device__ __forceinline__ float4 seg_ld4_any(const unsigned short* row,
+                                              int i4) {
+    return make_float4(bf16_up(row[4 * i4 + 0]), bf16_up(row[4 * i4 + 1]),
+                       bf16_up(row[4 * i4 + 2]), bf16_up(row[4 * i4 + 3]));
 }
 
 __device__ __forceinline__ float wave_reduce_sum(float v) {
@@ -146,4 +158,69 @@ __device__ __forceinline__ void seg_attn_row(
             seg_st(out_row, d, acc);
         }
     }
+}
+
+// Backward of seg_attn_row for the edges e in [lo, hi) of one destination,
+// given the gradient row g (D) of its output:
+//   dmsg[e] = att[e] * g ;  s_e = <msg_e, g> ;
+//   dgate[e] = att[e] * (s_e - sum_{e' in [lo, hi)} att[e'] s_e')
+// Shared by seg_attn_bwd (segops.hip: fp32 everywhere, s_e staged in dgate
+// itself, so `stage` and `dgate` may be the same buffer) and
+// attn_gamma_in_bwd_gate_kernel (mlp_glue.hip: bf16 g and msg, bf16 dgate,
+// fp32 stage, no dmsg).  Called by every thread of a SEG_BLOCK-thread
+// workgroup; an empty segment writes nothing.  WriteDmsg=false skips the
+// dmsg store and ignores `dmsg`.
+template <bool WriteDmsg, typename GradT, typename MsgT, typename DmsgT,
+          typename DgateT>
+__device__ __forceinline__ void seg_attn_bwd_row(
+        const GradT* __restrict__ g, const MsgT* __restrict__ msg,
+        const float* __restrict__ att, int lo, int hi, DmsgT* dmsg,
+        float* stage, DgateT* dgate, int D, float* red) {
+    const int deg = hi - lo;
+    if (deg == 0) return;
+    const int tid = threadIdx.x;
+    const int wid = tid / SEG_WAVE, lane = tid % SEG_WAVE;
+    const int n_waves = SEG_BLOCK / SEG_WAVE;
+
+    // pass 1: per-edge dmsg write + dot product (one wave per edge)
+    const bool vec4 = (D & 3) == 0;
+    for (int e = wid; e < deg; e += n_waves) {
+        const float ae = att[lo + e];
+        const MsgT* me = msg + (size_t)(lo + e) * D;
+        DmsgT* dme = WriteDmsg ? dmsg + (size_t)(lo + e) * D : nullptr;
+        float dot = 0.f;
+        if (vec4) {
+            const int D4 = D >> 2;
+            for (int d4 = lane; d4 < D4; d4 += SEG_WAVE) {
+                const float4 gv = seg_ld4_any(g, d4);
+                const float4 mv = seg_ld4(me, d4);
+                if (WriteDmsg) {
+                    float4 dv;
+                    dv.x = ae * gv.x; dv.y = ae * gv.y;
+                    dv.z = ae * gv.z; dv.w = ae * gv.w;
+                    seg_st4(dme, d4, dv);
+                }
+                dot += mv.x * gv.x + mv.y * gv.y + mv.z * gv.z + mv.w * gv.w;
+            }
+        } else {
+            for (int d = lane; d < D; d += SEG_WAVE) {
+                const float gv = seg_ld(g, d);
+                if (WriteDmsg) seg_st(dme, d, ae * gv);
+                dot += seg_ld(me, d) * gv;
+            }
+        }
+        dot = wave_reduce_sum(dot);
+        if (lane == 0) stage[lo + e] = dot;   // stage s_e
+    }
+    __syncthreads();
+
+    // seg = sum_e att_e * s_e
+    float part = 0.f;
+    for (int e = tid; e < deg; e += SEG_BLOCK)
+        part += att[lo + e] * stage[lo + e];
+    const float seg = block_reduce_sum(part, red, wid, lane);
+
+    // pass 2: dgate (overwrites the staged s_e where stage == dgate)
+    for (int e = tid; e < deg; e += SEG_BLOCK)
+        seg_st(dgate, lo + e, att[lo + e] * (stage[lo + e] - seg));
 }
