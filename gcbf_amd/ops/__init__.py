@@ -356,6 +356,57 @@ def rollout_tail(step_args, n_rec: int, comm_radius: float, attr_kind: int,
                      int(attr_dim), int(E_max), list(out), threads)
 
 
+def rollout_tail_batched_supported(B: int, n_rec: int,
+                                   num_nodes: int) -> bool:
+    """True where the extension is built and ``B`` scenes of ``n_rec``
+    receivers and ``num_nodes`` nodes each fit rollout_tail_batched.hip (one
+    workgroup per scene; bounds in docs/KERNELS.md)."""
+    ext = _load_ext()
+    if ext is None or not hasattr(ext, "rollout_tail_batched"):
+        return False
+    max_b, max_rows, max_nodes = ext.rollout_tail_batched_bounds()
+    return (1 <= B <= max_b and 1 <= n_rec <= max_rows
+            and num_nodes <= max_nodes)
+
+
+def rollout_tail_batched(step_args, explore: Tensor, n_rec: int,
+                         comm_radius: float, attr_kind: int, attr_dim: int,
+                         E_cap: int, out, threads: int = 1024) -> None:
+    """:func:`rollout_tail` for ``B`` scenes of one static layout, in two
+    launches of ``B`` workgroups (rollout_tail_batched.hip).  On ``states``
+    (B, N, S), ``goal`` (B, n, G), ``action`` (B, n, A) and ``explore``
+    (B,) int32 it is bit-equal to the kernel sequence
+
+        fused_masks(states.view(B*N, S), B, n_rec, r, kind,
+                    "unsafe").view(B, n_rec).any(1)
+        env_step_batched(kind, states, goal, where(explore, 0, action),
+                         active=ones(B), ...)
+        _C.build_graph_padded(new_states[..., :pos_dim], new_states, B,
+                              n_rec, comm_radius, -1, attr_kind, attr_dim,
+                              E_cap)
+
+    ``step_args`` is ``env.fused_step_args(...)`` on the batched tensors.
+    ``out`` is [new_states, u_ref_next, reward (B, n), reach, collision,
+    edge_index (2, E_cap), seg (E_cap,), edge_attr (E_cap, attr_dim), flags
+    int32 (B, 3), e_count int32 (1,)].  The edge list is the one globally
+    compacted list of ``build_graph_padded(batch=B)``: global node ids, all
+    pads (src = dst = 0, seg = B*N, attr = 0) after all real edges.
+    ``flags[b]`` is [scene b's edge count, all(reach[b]), unsafe_any[b]],
+    ``e_count`` the total.  GPU only: there is no eager twin, callers keep
+    the kernel sequence where this op does not apply.
+    """
+    ext = _require_ext("rollout_tail_batched")
+    if ext is None:
+        raise RuntimeError("rollout_tail_batched needs the HIP extension")
+    kind, states, goal, action, *rest = step_args
+    K = rest[0] if torch.is_tensor(rest[0]) else None
+    dt, r, sl, d2g, act_lim = rest[-5:]
+    ext.rollout_tail_batched(
+        _TAIL_KIND[kind], states, goal, action, explore, K, dt, r, sl, d2g,
+        act_lim, n_rec, float(comm_radius), int(attr_kind), int(attr_dim),
+        int(E_cap), list(out), threads)
+
+
 # --------------------------------------------------------------------------
 # MLP glue: padded bf16 GEMM inputs written directly (mlp_glue.hip)
 # --------------------------------------------------------------------------

@@ -98,6 +98,19 @@ extern "C" void launch_rollout_tail(
         float d2g, float act_lim, float r_comm, int attr_kind, int A_attr,
         long E_max, int threads, hipStream_t stream);
 
+extern "C" int rollout_tail_batched_max_rows();
+extern "C" int rollout_tail_batched_max_nodes();
+extern "C" int rollout_tail_batched_max_scenes();
+extern "C" void launch_rollout_tail_batched(
+        int kind, const float* states_in, const float* goal,
+        const float* action, const int* explore, const float* K,
+        float* states_out, float* u_ref_next, float* reward, bool* reach,
+        bool* collision, int* counts, long* edge_index, long* seg,
+        float* edge_attr, int* flags, int* e_count, int B, int N, int n,
+        int n_rec, int S, int G, int A, int P, float dt, float r_agent,
+        float sl, float d2g, float act_lim, float r_comm, int attr_kind,
+        int A_attr, long E_cap, int threads, hipStream_t stream);
+
 extern "C" void launch_edge_inputs_bf16(const float* x, const long* ei,
                                         const float* ea, void* out, int N,
                                         int nd, int ed, long E, long rows,
@@ -664,6 +677,120 @@ void rollout_tail(int64_t kind, torch::Tensor states, torch::Tensor goal,
         (int)attr_dim, E_max, (int)threads, current_stream());
 }
 
+// ---- batched rollout tail (rollout_tail_batched.hip): the same for B
+// scenes of one layout, two launches of B workgroups
+std::vector<int64_t> rollout_tail_batched_bounds() {
+    return {rollout_tail_batched_max_scenes(),
+            rollout_tail_batched_max_rows(),
+            rollout_tail_batched_max_nodes()};
+}
+
+void rollout_tail_batched(
+        int64_t kind, torch::Tensor states, torch::Tensor goal,
+        torch::Tensor action, torch::Tensor explore,
+        c10::optional<torch::Tensor> K, double dt, double r, double sl,
+        double d2g, double act_lim, int64_t n_rec, double comm_radius,
+        int64_t attr_kind, int64_t attr_dim, int64_t E_cap,
+        std::vector<torch::Tensor> out, int64_t threads) {
+    TORCH_CHECK(kind >= 0 && kind <= 2,
+                "rollout_tail_batched: unknown env kind ", kind);
+    const int64_t S = kind == 2 ? 6 : 4, P = kind == 2 ? 3 : 2;
+    const int64_t A = kind == 2 ? 3 : 2, G = kind == 0 ? 2 : S;
+    TORCH_CHECK(states.dim() == 3 && action.dim() == 3,
+                "rollout_tail_batched: states (B, N, S) and action "
+                "(B, n, A) expected");
+    const int64_t B = states.size(0), N = states.size(1),
+                  n = action.size(1);
+    TORCH_CHECK(B >= 1 && B <= rollout_tail_batched_max_scenes(),
+                "rollout_tail_batched: B must be in [1, ",
+                rollout_tail_batched_max_scenes(), "], got ", B);
+    CHECK_F32(states, B, N, S);
+    CHECK_F32(goal, B, n, G);
+    CHECK_F32(action, B, n, A);
+    CHECK_IN(explore);
+    TORCH_CHECK(explore.scalar_type() == torch::kInt32 &&
+                explore.dim() == 1 && explore.size(0) == B,
+                "rollout_tail_batched: explore must be int32 of shape (B,)");
+    TORCH_CHECK(n >= 1 && n <= N && (kind != 0 || n == N),
+                "rollout_tail_batched: bad agent count ", n, " for ", N,
+                " nodes");
+    const float* kptr = nullptr;
+    if (kind != 1) {
+        TORCH_CHECK(K.has_value(),
+                    "rollout_tail_batched: this env needs the gain K");
+        const torch::Tensor& Kt = K.value();
+        CHECK_F32(Kt, A, S);
+        kptr = Kt.data_ptr<float>();
+    }
+    TORCH_CHECK(n_rec >= 1 && n_rec <= n,
+                "rollout_tail_batched: n_rec must be in [1, n]");
+    TORCH_CHECK(n_rec <= rollout_tail_batched_max_rows() &&
+                N <= rollout_tail_batched_max_nodes(),
+                "rollout_tail_batched: scene (", n_rec, " receivers, ", N,
+                " nodes) above the one-workgroup-per-scene bound (",
+                rollout_tail_batched_max_rows(), ", ",
+                rollout_tail_batched_max_nodes(), ")");
+    TORCH_CHECK((attr_kind == 0 && attr_dim == S) ||
+                (attr_kind == 1 && S == 4 && attr_dim == 5),
+                "rollout_tail_batched: attr_kind/attr_dim mismatch");
+    TORCH_CHECK(E_cap >= 0 && E_cap <= B * n_rec * (N - 1) + 64,
+                "rollout_tail_batched: bad E_cap ", E_cap);
+    TORCH_CHECK(threads == 256 || threads == 512 || threads == 1024,
+                "rollout_tail_batched: threads must be 256, 512 or 1024");
+    TORCH_CHECK(out.size() == 10, "out must be {new_states, u_ref_next, "
+                "reward, reach, collision, edge_index, seg, edge_attr, "
+                "flags, e_count}");
+    const torch::Tensor &new_states = out[0], &u_ref_next = out[1],
+        &reward = out[2], &reach = out[3], &collision = out[4],
+        &edge_index = out[5], &seg = out[6], &edge_attr = out[7],
+        &flags = out[8], &e_count = out[9];
+    CHECK_F32(new_states, B, N, S);
+    CHECK_F32(u_ref_next, B, n, A);
+    CHECK_F32(reward, B, n);
+    CHECK_BOOL(reach, B, n);
+    CHECK_BOOL(collision, B, n);
+    CHECK_F32(edge_attr, E_cap, attr_dim);
+    CHECK_IN(edge_index); CHECK_IN(seg); CHECK_IN(flags); CHECK_IN(e_count);
+    TORCH_CHECK(edge_index.scalar_type() == torch::kInt64 &&
+                seg.scalar_type() == torch::kInt64 &&
+                edge_index.sizes() == torch::IntArrayRef({2, E_cap}) &&
+                seg.sizes() == torch::IntArrayRef({E_cap}),
+                "rollout_tail_batched: edge_index (2, E_cap) / seg (E_cap,) "
+                "int64 expected");
+    TORCH_CHECK(flags.scalar_type() == torch::kInt32 &&
+                flags.sizes() == torch::IntArrayRef({B, 3}),
+                "rollout_tail_batched: flags must be int32 (B, 3)");
+    TORCH_CHECK(e_count.scalar_type() == torch::kInt32 &&
+                e_count.numel() == 1,
+                "rollout_tail_batched: e_count must be int32 (1,)");
+    const auto dev = states.device();
+    for (const torch::Tensor& t : out)
+        TORCH_CHECK(t.device() == dev,
+                    "rollout_tail_batched: all tensors must be on one device");
+    TORCH_CHECK(goal.device() == dev && action.device() == dev &&
+                explore.device() == dev,
+                "rollout_tail_batched: all tensors must be on one device");
+    TORCH_CHECK(!K.has_value() || K->device() == dev,
+                "rollout_tail_batched: all tensors must be on one device");
+    TORCH_CHECK(new_states.data_ptr() != states.data_ptr(),
+                "rollout_tail_batched: new_states must not alias states");
+    // per-row counts: the hand-over between the two launches
+    auto counts = torch::empty({B * n_rec},
+                               states.options().dtype(torch::kInt32));
+    launch_rollout_tail_batched(
+        (int)kind, states.data_ptr<float>(), goal.data_ptr<float>(),
+        action.data_ptr<float>(), explore.data_ptr<int>(), kptr,
+        new_states.data_ptr<float>(), u_ref_next.data_ptr<float>(),
+        reward.data_ptr<float>(), reach.data_ptr<bool>(),
+        collision.data_ptr<bool>(), counts.data_ptr<int>(),
+        edge_index.data_ptr<int64_t>(), seg.data_ptr<int64_t>(),
+        edge_attr.data_ptr<float>(), flags.data_ptr<int>(),
+        e_count.data_ptr<int>(), (int)B, (int)N, (int)n, (int)n_rec, (int)S,
+        (int)G, (int)A, (int)P, (float)dt, (float)r, (float)sl, (float)d2g,
+        (float)act_lim, (float)comm_radius, (int)attr_kind, (int)attr_dim,
+        E_cap, (int)threads, current_stream());
+}
+
 // ---- MLP glue (mlp_glue.hip): padded bf16 GEMM inputs written directly
 torch::Tensor edge_inputs_bf16(torch::Tensor x, torch::Tensor edge_index,
                                torch::Tensor edge_attr, int64_t rows_padded) {
@@ -1006,6 +1133,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "greedy rejection sampling over a candidate pool (episode reset)",
           py::arg("cand"), py::arg("min_sep"), py::arg("avoid"),
           py::arg("avoid_dist"), py::arg("pts"), py::arg("count"));
+    m.def("rollout_tail_batched", &rollout_tail_batched,
+          "mask -> env step -> padded graph rebuild -> flags for B scenes, "
+          "two launches of B workgroups",
+          py::arg("kind"), py::arg("states"), py::arg("goal"),
+          py::arg("action"), py::arg("explore"), py::arg("K"),
+          py::arg("dt"), py::arg("r"), py::arg("sl"), py::arg("d2g"),
+          py::arg("act_lim"), py::arg("n_rec"), py::arg("comm_radius"),
+          py::arg("attr_kind"), py::arg("attr_dim"), py::arg("E_cap"),
+          py::arg("out"), py::arg("threads") = 1024);
+    m.def("rollout_tail_batched_bounds", &rollout_tail_batched_bounds,
+          "(max scenes, max receiver rows, max nodes per scene)");
     m.def("rollout_tail", &rollout_tail,
           "mask -> env step -> padded graph rebuild -> flags, one launch",
           py::arg("kind"), py::arg("states"), py::arg("goal"),

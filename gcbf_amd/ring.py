@@ -68,6 +68,24 @@ class RingStore:
         self.next_id += 1
         return rid
 
+    def push_raw_many(self, states, u_ref) -> list:
+        """:meth:`push_raw` for ``B`` graphs at once: ``states`` (B, N, S)
+        and ``u_ref`` (B, n, ad) go into the next B consecutive slots, in
+        order; returns their ring ids.  At most two copies per tensor (the
+        second one when the slots wrap around at ``CAP``)."""
+        B = states.shape[0]
+        assert B <= self.CAP, "more graphs than ring slots"
+        slot = self.next_id % self.CAP
+        head = min(B, self.CAP - slot)
+        self.states[slot:slot + head].copy_(states[:head], non_blocking=True)
+        self.uref[slot:slot + head].copy_(u_ref[:head], non_blocking=True)
+        if head < B:
+            self.states[:B - head].copy_(states[head:], non_blocking=True)
+            self.uref[:B - head].copy_(u_ref[head:], non_blocking=True)
+        ids = list(range(self.next_id, self.next_id + B))
+        self.next_id += B
+        return ids
+
     def resident(self, ring_id: int) -> bool:
         return ring_id is not None and self.next_id - ring_id <= self.CAP
 

@@ -26,7 +26,8 @@ class Trainer:
 
     def __init__(self, env: MultiAgentEnv, env_test: MultiAgentEnv,
                  algo: Algorithm, log_dir: str, rank: int = 0,
-                 world_size: int = 1, eval_batch: bool = False):
+                 world_size: int = 1, eval_batch: bool = False,
+                 num_envs: int = 1):
         self.env = env
         self.env_test = env_test
         self.algo = algo
@@ -35,6 +36,21 @@ class Trainer:
         self.world_size = world_size
         # opt-in: run the eval episodes as one SceneBatch
         self.eval_batch = eval_batch
+        # opt-in: collect from num_envs scenes per captured step
+        # (gcbf_amd/vec_rollout.py); 1 keeps the single-scene loop
+        self.num_envs = int(num_envs)
+        if self.num_envs < 1:
+            raise ValueError("num_envs must be at least 1")
+        if self.num_envs > 1:
+            if world_size > 1:
+                raise ValueError(
+                    "num_envs > 1 together with world_size > 1 is untested "
+                    "and refused: use one rank, or num_envs=1")
+            batch_size = getattr(algo, "batch_size", None)
+            if batch_size is not None and batch_size % self.num_envs != 0:
+                raise ValueError(
+                    f"batch_size ({batch_size}) must be a multiple of "
+                    f"num_envs ({self.num_envs})")
 
         if rank == 0:
             os.makedirs(log_dir, exist_ok=True)
@@ -62,6 +78,11 @@ class Trainer:
 
     def train(self, steps: int, eval_interval: int, eval_epi: int,
               start_step: int = 1, capture: bool = True):
+        if self.num_envs > 1:
+            engine = self._make_vec_engine()
+            if engine is not None:
+                return self._train_vec(engine, steps, eval_interval,
+                                       eval_epi, start_step)
         start_time = time.time()
         data = self.env.reset()
         engine = self._make_engine() if capture else None
@@ -100,23 +121,89 @@ class Trainer:
                 last_report, steps_since_report = now, 0
 
             if step % eval_interval == 0:
-                if eval_epi > 0 and self.rank == 0:
-                    reward_mean, eval_info = self.eval(step, eval_epi)
-                    msg = (f"step: {step}, time: "
-                           f"{time.time() - start_time:.0f}s, "
-                           f"reward: {reward_mean:.2f}")
-                    for key, val in eval_info.items():
-                        msg += f", {key}: {val}"
-                    print(msg, flush=True)
-                if verbose is not None and self.rank == 0:
-                    print("step: " + str(step) + "".join(
-                        f", {k}: {v:.3f}" for k, v in verbose.items()),
-                        flush=True)
-                if self.rank == 0:
-                    self.algo.save(os.path.join(self.model_dir,
-                                                f"step_{step}"))
-                    self._save_trainer_state(step)
-                self.algo._env = self.env
+                self._eval_and_save(step, eval_epi, start_time, verbose)
+
+        if self.rank == 0:
+            print(f"> Done in {time.time() - start_time:.0f} seconds",
+                  flush=True)
+
+    def _eval_and_save(self, step: int, eval_epi: int, start_time: float,
+                       verbose):
+        if eval_epi > 0 and self.rank == 0:
+            reward_mean, eval_info = self.eval(step, eval_epi)
+            msg = (f"step: {step}, time: "
+                   f"{time.time() - start_time:.0f}s, "
+                   f"reward: {reward_mean:.2f}")
+            for key, val in eval_info.items():
+                msg += f", {key}: {val}"
+            print(msg, flush=True)
+        if verbose is not None and self.rank == 0:
+            print("step: " + str(step) + "".join(
+                f", {k}: {v:.3f}" for k, v in verbose.items()),
+                flush=True)
+        if self.rank == 0:
+            self.algo.save(os.path.join(self.model_dir, f"step_{step}"))
+            self._save_trainer_state(step)
+        self.algo._env = self.env
+
+    # ------------------------------------------------- vectorized collection
+    def _make_vec_engine(self):
+        """The B-scene engine, or None (with the reason printed) where it
+        does not apply: the single-scene path then runs as always."""
+        from ..vec_rollout import (VecRolloutEngine,
+                                   vec_engine_unsupported_reason)
+        if self.env.data is None:
+            self.env.reset()
+        reason = vec_engine_unsupported_reason(self.env, self.algo,
+                                               self.num_envs)
+        if reason is None:
+            try:
+                return VecRolloutEngine(self.env, self.algo, self.num_envs)
+            except Exception as e:
+                reason = str(e)
+        if self.rank == 0:
+            print(f"> vectorized rollout unavailable ({reason}); "
+                  f"using the single-scene path", flush=True)
+        return None
+
+    def _train_vec(self, engine, steps: int, eval_interval: int,
+                   eval_epi: int, start_step: int):
+        """The training loop over B scenes per engine step: ``step`` counts
+        env steps and advances by B.  The engine's pending snapshots are
+        flushed into the buffer before every update, which comes when
+        ``step`` reaches a multiple of the algorithm's batch size; eval and
+        save when it crosses a multiple of ``eval_interval``."""
+        B = engine.B
+        start_time = time.time()
+        if self.rank == 0:
+            print(f"> vectorized rollout engine active ({B} scenes, "
+                  f"{'captured' if engine.g is not None else 'plain'} "
+                  f"body)", flush=True)
+        batch_size = self.algo.batch_size
+        last_report = start_time
+        steps_since_report = 0
+        verbose = None
+        step = start_step - 1           # env steps taken so far
+        while step < steps:
+            # exploration probability of the group's first env step
+            engine.step(prob=1 - step / steps)
+            prev, step = step, step + B
+
+            if step // batch_size > prev // batch_size:
+                engine.flush()
+                verbose = self.algo.update(step, self.writer)
+
+            steps_since_report += B
+            now = time.time()
+            if now - last_report > 30 and self.rank == 0:
+                rate = steps_since_report / (now - last_report)
+                self.writer.add_scalar("perf/env_steps_per_sec", rate, step)
+                print(f"step {step}/{steps} | {rate:.1f} env-steps/s "
+                      f"({B} scenes)", flush=True)
+                last_report, steps_since_report = now, 0
+
+            if step // eval_interval > prev // eval_interval:
+                self._eval_and_save(step, eval_epi, start_time, verbose)
 
         if self.rank == 0:
             print(f"> Done in {time.time() - start_time:.0f} seconds",

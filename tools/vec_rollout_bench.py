@@ -1,0 +1,146 @@
+"""Vectorized-rollout benchmark: env-steps/s against the single-scene engine.
+
+    python tools/vec_rollout_bench.py [--env DubinsCar] [-n 16] [--obs 0]
+                                      [--envs 1 4 16] [--rounds 3]
+                                      [--rollout-steps 1024]
+                                      [--train-steps 1024] [--batch-size 512]
+
+Two figures per engine, on one process and one set of weights:
+
+* rollout-only env-steps/s: engine steps at prob 0.5, no updates;
+* whole-training env-steps/s: collection plus one ``algo.update`` per
+  ``--batch-size`` env steps, the update's cost amortized over the steps
+  that fed it.
+
+The baseline is ``RolloutEngine`` (one scene per replay).  Every round
+measures the baseline and then each ``VecRolloutEngine(B)``, so the
+``--rounds`` samples of each configuration alternate in time with the
+baseline's.  The ranges (min..max over the rounds) are printed, and a gain
+is claimed for a B only where its range lies wholly above the baseline's.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+from gcbf_amd.algo import make_algo
+from gcbf_amd.env import make_env
+from gcbf_amd.rollout import RolloutEngine
+from gcbf_amd.trainer.utils import set_seed
+from gcbf_amd.utils.amp import enable_bf16
+from gcbf_amd.vec_rollout import VecRolloutEngine
+
+
+class _Single:
+    """RolloutEngine behind the vectorized engine's interface."""
+    B = 1
+
+    def __init__(self, env, algo):
+        self.eng = RolloutEngine(env, algo)
+
+    def step(self, prob):
+        if self.eng.step(prob=prob):
+            self.eng.reload()
+
+    def flush(self):
+        pass
+
+
+def _collect(engine, env_steps, prob=0.5):
+    for _ in range(env_steps // engine.B):
+        engine.step(prob)
+
+
+def rollout_rate(engine, env_steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _collect(engine, env_steps)
+    torch.cuda.synchronize()
+    return env_steps / (time.perf_counter() - t0)
+
+
+def training_rate(engine, algo, env_steps, batch_size):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(env_steps // batch_size):
+        _collect(engine, batch_size)
+        engine.flush()
+        algo.update((k + 1) * batch_size, None)
+    torch.cuda.synchronize()
+    return env_steps / (time.perf_counter() - t0)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--env", type=str, default="DubinsCar")
+    p.add_argument("-n", "--num-agents", type=int, default=16)
+    p.add_argument("--obs", type=int, default=0)
+    p.add_argument("--envs", type=int, nargs="+", default=[1, 4, 16])
+    p.add_argument("--rounds", type=int, default=3)
+    p.add_argument("--rollout-steps", type=int, default=1024)
+    p.add_argument("--train-steps", type=int, default=1024)
+    p.add_argument("--batch-size", type=int, default=512)
+    args = p.parse_args()
+    assert all(args.batch_size % b == 0 for b in args.envs)
+
+    set_seed(0)
+    dev = torch.device("cuda")
+    params = make_env(args.env, args.num_agents, dev).default_params
+    params["num_obs"] = args.obs
+    env = make_env(args.env, args.num_agents, dev, params=params)
+    env.train()
+    algo = make_algo("gcbf", env, args.num_agents, env.node_dim,
+                     env.edge_dim, env.action_dim, dev,
+                     batch_size=args.batch_size)
+    enable_bf16(algo)
+    env.reset()
+
+    engines = {"single": _Single(env, algo)}
+    for b in args.envs:
+        engines[f"vec{b}"] = VecRolloutEngine(env, algo, b)
+    # warmup: every engine, and one update (builds the ring batches' plans)
+    for eng in engines.values():
+        _collect(eng, 256)
+        eng.flush()
+    algo.update(args.batch_size, None)
+
+    res = {k: {"rollout": [], "training": []} for k in engines}
+    for _ in range(args.rounds):
+        for name, eng in engines.items():
+            res[name]["rollout"].append(
+                rollout_rate(eng, args.rollout_steps))
+            eng.flush()
+            algo.buffer.clear()
+        for name, eng in engines.items():
+            res[name]["training"].append(
+                training_rate(eng, algo, args.train_steps, args.batch_size))
+
+    print(f"# {args.env} n={args.num_agents} obs={args.obs}, "
+          f"{args.rounds} alternated rounds, env-steps/s min..max")
+    for metric in ("rollout", "training"):
+        base = res["single"][metric]
+        for name in engines:
+            v = res[name][metric]
+            verdict = ""
+            if name != "single":
+                if min(v) > max(base):
+                    verdict = f"  gain x{min(v) / max(base):.2f}.." \
+                              f"{max(v) / min(base):.2f} (ranges disjoint)"
+                elif max(v) < min(base):
+                    verdict = "  slower (ranges disjoint)"
+                else:
+                    verdict = "  no claim (ranges overlap)"
+            print(f"{metric:9s} {name:7s} {min(v):10.1f} .. {max(v):10.1f}"
+                  f"{verdict}")
+    print(json.dumps({"env": args.env, "n": args.num_agents,
+                      "obs": args.obs, "batch_size": args.batch_size,
+                      "results": res}))
+
+
+if __name__ == "__main__":
+    main()

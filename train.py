@@ -98,7 +98,7 @@ def train(args):
 
     trainer = Trainer(env=env, env_test=env_test, algo=algo, log_dir=log_path,
                       rank=rank, world_size=world_size,
-                      eval_batch=args.eval_batch)
+                      eval_batch=args.eval_batch, num_envs=args.num_envs)
     start_step = 1
     if args.resume is not None:
         model_dir = os.path.join(log_path, "models")
@@ -145,4 +145,8 @@ if __name__ == "__main__":
     parser.add_argument("--eval-batch", action="store_true", default=False,
                         help="run the --eval-epi evaluation episodes as one "
                              "scene batch (batched step kernel)")
+    parser.add_argument("--num-envs", type=int, default=1,
+                        help="collect from this many independent scenes per "
+                             "captured rollout step (--batch-size must be a "
+                             "multiple of it; 1: the single-scene engine)")
     train(parser.parse_args())
