@@ -228,14 +228,55 @@ torch::Tensor segment_max_bwd(torch::Tensor grad_out, torch::Tensor argmax,
     return dval;
 }
 
+// Argument checks shared by build_graph and build_graph_padded; every one
+// fires before the first launch.  Returns N, the nodes per graph.
+static int64_t check_graph_args(const torch::Tensor& pos,
+                                const torch::Tensor& states, int64_t B,
+                                int64_t n_rec, int64_t attr_kind,
+                                int64_t attr_dim) {
+    CHECK_IN(pos);
+    CHECK_IN(states);
+    TORCH_CHECK(pos.scalar_type() == torch::kFloat32, "pos must be fp32");
+    TORCH_CHECK(states.scalar_type() == torch::kFloat32,
+                "states must be fp32");
+    TORCH_CHECK(pos.dim() == 2 && states.dim() == 2,
+                "pos and states must be 2-D");
+    TORCH_CHECK(pos.device() == states.device(),
+                "pos and states must share a device");
+    TORCH_CHECK(B >= 1, "B must be >= 1 (got ", B, ")");
+    TORCH_CHECK(pos.size(0) % B == 0, "pos rows (", pos.size(0),
+                ") must be a multiple of B (", B, ")");
+    TORCH_CHECK(states.size(0) == pos.size(0), "states rows (",
+                states.size(0), ") != pos rows (", pos.size(0), ")");
+    const int64_t N = pos.size(0) / B;
+    const int64_t P = pos.size(1), S = states.size(1);
+    TORCH_CHECK(P >= 1 && P <= S, "need 1 <= P <= S (got P=", P, ", S=", S,
+                ")");
+    TORCH_CHECK(n_rec >= 0 && n_rec <= N, "need 0 <= n_rec <= N (got n_rec=",
+                n_rec, ", N=", N, ")");
+    TORCH_CHECK(attr_kind == 0 || attr_kind == 1,
+                "attr_kind must be 0 (diff) or 1 (dubins), got ", attr_kind);
+    if (attr_kind == 0) {
+        TORCH_CHECK(attr_dim == S, "ATTR_DIFF needs attr_dim == S (got ",
+                    attr_dim, " vs ", S, ")");
+    } else {
+        TORCH_CHECK(S == 4 && attr_dim == 5,
+                    "ATTR_DUBINS needs S == 4 and attr_dim == 5 (got S=", S,
+                    ", attr_dim=", attr_dim, ")");
+    }
+    return N;
+}
+
 std::vector<torch::Tensor> build_graph(torch::Tensor pos,
                                        torch::Tensor states, int64_t B,
                                        int64_t n_rec, double r, int64_t topk,
                                        int64_t attr_kind, int64_t attr_dim) {
-    CHECK_IN(pos);
-    CHECK_IN(states);
-    const int64_t N = pos.size(0) / B;
+    const int64_t N = check_graph_args(pos, states, B, n_rec, attr_kind,
+                                       attr_dim);
     const int64_t P = pos.size(1), S = states.size(1);
+    if (B * n_rec == 0)  // no receiver rows: nothing to launch
+        return {torch::empty({2, 0}, pos.options().dtype(torch::kInt64)),
+                torch::empty({0, attr_dim}, pos.options())};
     auto stream = current_stream();
     auto counts = torch::empty({B * n_rec},
                                pos.options().dtype(torch::kInt32));
@@ -244,7 +285,7 @@ std::vector<torch::Tensor> build_graph(torch::Tensor pos,
                         (int)topk, stream);
     auto incl = counts.cumsum(0, torch::kInt32);
     auto offsets = (incl - counts).contiguous();
-    const int64_t E = incl.numel() ? incl[-1].item<int64_t>() : 0;
+    const int64_t E = incl[-1].item<int64_t>();
     auto edge_index = torch::empty({2, E},
                                    pos.options().dtype(torch::kInt64));
     auto edge_attr = torch::empty({E, attr_dim}, pos.options());
@@ -286,18 +327,10 @@ std::vector<torch::Tensor> build_graph_padded(
         int64_t E_max,
         c10::optional<std::vector<torch::Tensor>> out_opt = c10::nullopt) {
     // capture-safe variant: fixed E_max edge buffers, no host sync.
-    CHECK_IN(pos);
-    CHECK_IN(states);
-    const int64_t N = pos.size(0) / B;
+    const int64_t N = check_graph_args(pos, states, B, n_rec, attr_kind,
+                                       attr_dim);
+    TORCH_CHECK(E_max >= 0, "E_max must be >= 0 (got ", E_max, ")");
     const int64_t P = pos.size(1), S = states.size(1);
-    auto stream = current_stream();
-    auto counts = torch::empty({B * n_rec},
-                               pos.options().dtype(torch::kInt32));
-    launch_radius_count(pos.data_ptr<float>(), counts.data_ptr<int>(),
-                        (int)B, (int)N, (int)n_rec, (int)P, (float)r,
-                        (int)topk, stream);
-    auto incl = counts.cumsum(0, torch::kInt32);
-    auto offsets = (incl - counts).contiguous();
     torch::Tensor edge_index, seg, edge_attr, e_count;
     if (out_opt.has_value()) {
         TORCH_CHECK(out_opt->size() == 4,
@@ -307,8 +340,22 @@ std::vector<torch::Tensor> build_graph_padded(
         seg = (*out_opt)[1];
         edge_attr = (*out_opt)[2];
         e_count = (*out_opt)[3];
+        TORCH_CHECK(edge_index.scalar_type() == torch::kInt64
+                    && seg.scalar_type() == torch::kInt64,
+                    "out edge_index and seg must be int64");
+        TORCH_CHECK(edge_attr.scalar_type() == torch::kFloat32,
+                    "out edge_attr must be fp32");
+        TORCH_CHECK(e_count.scalar_type() == torch::kInt32,
+                    "out e_count must be int32");
+        TORCH_CHECK(edge_index.dim() == 2 && edge_index.size(0) == 2
+                    && seg.dim() == 1 && edge_attr.dim() == 2,
+                    "out must be edge_index (2, E_max), seg (E_max,), "
+                    "edge_attr (E_max, attr_dim)");
         TORCH_CHECK(edge_index.size(1) == E_max && seg.size(0) == E_max
                     && edge_attr.size(0) == E_max, "E_max mismatch");
+        TORCH_CHECK(edge_attr.size(1) == attr_dim, "out edge_attr has ",
+                    edge_attr.size(1), " columns, attr_dim is ", attr_dim);
+        TORCH_CHECK(e_count.numel() == 1, "out e_count must hold 1 element");
     } else {
         edge_index = torch::empty({2, E_max},
                                   pos.options().dtype(torch::kInt64));
@@ -316,6 +363,22 @@ std::vector<torch::Tensor> build_graph_padded(
         edge_attr = torch::empty({E_max, attr_dim}, pos.options());
         e_count = torch::empty({1}, pos.options().dtype(torch::kInt32));
     }
+    if (B * n_rec == 0) {
+        // no receiver rows: every entry is a pad, nothing to launch
+        edge_index.zero_();
+        seg.fill_(B * N);
+        edge_attr.zero_();
+        e_count.zero_();
+        return {edge_index, seg, edge_attr, e_count};
+    }
+    auto stream = current_stream();
+    auto counts = torch::empty({B * n_rec},
+                               pos.options().dtype(torch::kInt32));
+    launch_radius_count(pos.data_ptr<float>(), counts.data_ptr<int>(),
+                        (int)B, (int)N, (int)n_rec, (int)P, (float)r,
+                        (int)topk, stream);
+    auto incl = counts.cumsum(0, torch::kInt32);
+    auto offsets = (incl - counts).contiguous();
     launch_radius_fill(pos.data_ptr<float>(), states.data_ptr<float>(),
                        offsets.data_ptr<int>(),
                        edge_index.data_ptr<int64_t>(),
@@ -337,16 +400,24 @@ torch::Tensor fused_linear(torch::Tensor x, torch::Tensor w,
     CHECK_IN(w);
     TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "x must be bf16");
     TORCH_CHECK(w.scalar_type() == torch::kBFloat16, "w must be bf16");
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x and w must be 2-D");
     const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
     TORCH_CHECK(w.size(1) == K, "K mismatch");
     TORCH_CHECK(M % 128 == 0 && N % 128 == 0 && K % 64 == 0,
                 "fused_linear needs M%128==0, N%128==0, K%64==0 (got ", M,
                 "x", K, " -> ", N, ")");
+    TORCH_CHECK(M > 0 && N > 0 && K > 0,
+                "fused_linear needs M, N, K > 0 (got ", M, "x", K, " -> ", N,
+                ")");
+    TORCH_CHECK(act >= 0 && act <= 2,
+                "act must be 0 (none), 1 (relu) or 2 (tanh), got ", act);
     const float* bptr = nullptr;
     if (bias.has_value()) {
         CHECK_IN(bias.value());
         TORCH_CHECK(bias->scalar_type() == torch::kFloat32,
                     "bias must be fp32");
+        TORCH_CHECK(bias->numel() == N, "bias has ", bias->numel(),
+                    " elements, N is ", N);
         bptr = bias->data_ptr<float>();
     }
     auto out = torch::empty({M, N}, x.options().dtype(

@@ -141,7 +141,8 @@ extern "C" __global__ __launch_bounds__(THREADS, 2) void fused_linear_bf16(
             for (int rg = 0; rg < 4; ++rg) {
                 const int row = bm + wr + mi * 16 + crow + rg;
                 float v = acc[mi][ni][rg] + b;
-                if (act == ACT_RELU) v = fmaxf(v, 0.f);
+                // not fmaxf: a NaN pre-activation stays NaN, as torch.relu
+                if (act == ACT_RELU) v = v < 0.f ? 0.f : v;
                 else if (act == ACT_TANH) v = tanhf(v);
                 if (out_f32)
                     Cf[(size_t)row * N + col] = v;
