@@ -53,6 +53,12 @@ class Algorithm(ABC):
     def step(self, data: GraphBatch, prob: float) -> Tensor:
         """Training-time action (with exploration and buffer bookkeeping)."""
 
+    def explore_prob(self, prob: float) -> float:
+        """Probability with which :meth:`step` explores when handed
+        ``prob``; a rollout engine that draws the exploration decision
+        itself asks here, so both loops consume the same random stream."""
+        return prob
+
     def post_step(self, data: GraphBatch, action: Tensor, reward, done: bool,
                   next_data: GraphBatch):
         pass

@@ -55,6 +55,10 @@ class MACBF(GCBF):
         self.buffer = Buffer()
         self.memory = Buffer()
 
+    def explore_prob(self, prob: float) -> float:
+        # the floor :meth:`step` applies (reference macbf.py:109)
+        return max(prob, 0.5)
+
     @torch.no_grad()
     def step(self, data: GraphBatch, prob: float) -> Tensor:
         # exploration probability floored at 0.5 (reference macbf.py:109)

@@ -255,10 +255,53 @@ class MACBFControllerLayer(nn.Module):
                          hidden_layers=(64, 128, 64))
 
     def forward(self, x: Tensor, edge_attr: Tensor, edge_index: Tensor,
-                node_mask: Optional[Tensor] = None) -> Tensor:
+                node_mask=None, seg_dst: Optional[Tensor] = None) -> Tensor:
         num_nodes = x.shape[0]
         msg = self.phi(_gather_edge_inputs(x, edge_attr, edge_index))
-        aggr = ops.segment_max(msg, edge_index[1], num_nodes)
+        # seg_dst: segment ids of a padded edge list, whose pad entries
+        # carry the sentinel id num_nodes and fall outside every segment
+        dst = edge_index[1] if seg_dst is None else seg_dst
+        aggr = ops.segment_max(msg, dst, num_nodes)
         if node_mask is not None:
-            aggr = aggr[node_mask]
+            # int = "first n rows" static slice, LONG tensor = static row
+            # indices (both capture-safe); boolean mask otherwise
+            aggr = (aggr[:node_mask] if isinstance(node_mask, int)
+                    else aggr[node_mask])
         return self.gamma(aggr)
+
+    def glue_applies(self, x: Tensor, edge_index: Tensor, node_mask) -> bool:
+        """Whether :meth:`forward_padded_bf16` computes this call: no-grad
+        GPU inference on the library-GEMM plans with a static row layout."""
+        from . import fused
+        bucket = MLP.BUCKET
+        rows = _glue_rows(x, node_mask)
+        E = edge_index.shape[1]
+        return (rows is not None and rows[0] > 0 and E > 0
+                and not torch.is_grad_enabled() and x.is_cuda
+                and ops.hip_available()
+                and all(m.fused_mfma and fused.plan_is_plain(
+                            m._plan, -(-r // bucket) * bucket)
+                        for m, r in ((self.phi, E), (self.gamma, rows[0]))))
+
+    def forward_padded_bf16(self, x: Tensor, edge_attr: Tensor,
+                            edge_index: Tensor, node_mask,
+                            seg_dst: Tensor) -> Tensor:
+        """No-grad forward that never leaves padded bf16 between the GEMMs:
+        γ's output for the rows ``node_mask`` selects (every node, the first
+        n, or LONG indices) as bf16 rows padded to the GEMM bucket.  Same
+        GEMM calls on the same operand values as :meth:`forward`; the
+        gathers, cat, pads, casts, CSR pointer, segment max and row select
+        between them are two glue kernels (ops/hip/mlp_glue.hip,
+        ops/hip/macbf_glue.hip).  φ's pad rows are never read: the segment
+        max scans real edges only."""
+        from . import fused
+        bucket = MLP.BUCKET
+        n_rows, idx = _glue_rows(x, node_mask)
+        rows_e = -(-edge_index.shape[1] // bucket) * bucket
+        rows_n = -(-n_rows // bucket) * bucket
+        msg = fused.run_plan_padded_bf16(
+            self.phi._plan,
+            ops.edge_inputs_bf16(x, edge_index, edge_attr, rows_e))
+        gamma_in = ops.segmax_rows_bf16(
+            msg, seg_dst, n_rows if idx is None else idx, x.shape[0], rows_n)
+        return fused.run_plan_padded_bf16(self.gamma._plan, gamma_in)

@@ -152,7 +152,9 @@ class _SegmentMaxHip(torch.autograd.Function):
 class _SegmentMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, values: Tensor, dst: Tensor, num_nodes: int):
-        out = eager.segment_max(values.detach(), dst, num_nodes)
+        # one extra row absorbs sentinel destinations (padded edge lists
+        # use dst == num_nodes for invalid entries), as in eager.segment_sum
+        out = eager.segment_max(values.detach(), dst, num_nodes + 1)
         # argmax for backward: first edge attaining the max in its segment
         sel = out.index_select(0, dst)
         is_max = (values.detach() == sel)
@@ -161,13 +163,13 @@ class _SegmentMax(torch.autograd.Function):
         big = values.shape[0] + 1
         cand = torch.where(is_max, order.unsqueeze(1), torch.full_like(
             is_max, big, dtype=torch.long))
-        first = torch.full((num_nodes, values.shape[1]), big, dtype=torch.long,
-                           device=values.device)
+        first = torch.full((num_nodes + 1, values.shape[1]), big,
+                           dtype=torch.long, device=values.device)
         first = first.scatter_reduce(0, dst.unsqueeze(1).expand_as(cand), cand,
                                      reduce="amin", include_self=True)
-        ctx.save_for_backward(dst, first)
+        ctx.save_for_backward(dst, first[:num_nodes])
         ctx.E = values.shape[0]
-        return out
+        return out[:num_nodes]
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
@@ -327,15 +329,19 @@ def rollout_tail_supported(n_rec: int, num_nodes: int) -> bool:
 
 
 def rollout_tail(step_args, n_rec: int, comm_radius: float, attr_kind: int,
-                 attr_dim: int, E_max: int, out, threads: int = 1024) -> None:
+                 attr_dim: int, E_max: int, out, threads: int = 1024,
+                 topk: int = -1) -> None:
     """Everything a captured rollout step does after the actor, in one
     launch (rollout_tail.hip), bit-equal to the kernel sequence
 
         fused_masks(states, 1, n_rec, r, kind, "unsafe").any()
         env_step_fused(*step_args)
         _C.build_graph_padded(new_states[:, :pos_dim], new_states, 1, n_rec,
-                              comm_radius, -1, attr_kind, attr_dim, E_max)
+                              comm_radius, topk, attr_kind, attr_dim, E_max)
         reach.all()
+
+    ``topk`` caps every receiver at its k nearest senders, ties at the k-th
+    distance kept (the env's ``max_neighbors``); -1 is no cap.
 
     ``step_args`` is ``env.fused_step_args(...)``.  ``out`` is [new_states,
     u_ref_next, reward, reach, collision, edge_index (2, E_max), seg
@@ -353,7 +359,8 @@ def rollout_tail(step_args, n_rec: int, comm_radius: float, attr_kind: int,
                      action.contiguous(),
                      None if K is None else K.contiguous(), dt, r, sl,
                      d2g, act_lim, n_rec, float(comm_radius), int(attr_kind),
-                     int(attr_dim), int(E_max), list(out), threads)
+                     int(attr_dim), int(E_max), list(out), threads,
+                     topk=int(topk))
 
 
 def rollout_tail_batched_supported(B: int, n_rec: int,
@@ -471,6 +478,35 @@ def rows_cat_pad_bf16(a: Tensor, b: Tensor, n_rows: int,
                                          n_rows, rows_padded)
     rows = torch.cat([a[:n_rows], b[:n_rows].bfloat16()], dim=1)
     return _pad_rows(rows, rows_padded)
+
+
+def segmax_rows_bf16(msg: Tensor, seg: Tensor, row_index_or_n,
+                     num_nodes: int, rows_padded: int) -> Tensor:
+    """bf16 (rows_padded, D): row r is the element-wise max over the
+    messages whose ``seg`` equals row r's node id, 0 for an empty segment;
+    rows past the row count are zero.  Row r's node is r for an int
+    ``row_index_or_n`` (the first n nodes) or ``row_index_or_n[r]`` for a
+    LONG index tensor.  ``msg`` is bf16 with at least ``len(seg)`` rows
+    (rows past the real edges may hold anything), ``seg`` is dst-sorted with
+    sentinel entries == ``num_nodes`` at the end.  Forward only.  One launch
+    (macbf_glue.hip) for the CSR pointer, :func:`segment_max`, its casts,
+    the row select and the pad; same comparison as ``seg_max_fwd``."""
+    if torch.is_tensor(row_index_or_n):
+        idx, n_rows = row_index_or_n, row_index_or_n.shape[0]
+    else:
+        idx, n_rows = None, int(row_index_or_n)
+    if msg.is_cuda:
+        ext = _require_ext("segmax_rows_bf16")
+        if ext is not None:
+            return ext.segmax_rows_bf16(
+                msg.contiguous(), seg.contiguous(),
+                None if idx is None else idx.contiguous(), n_rows,
+                num_nodes, rows_padded)
+    E = seg.shape[0]
+    real = seg < num_nodes          # drop the sentinel entries
+    aggr = segment_max(msg[:E][real].float(), seg[real], num_nodes)
+    rows = aggr[:n_rows] if idx is None else aggr.index_select(0, idx)
+    return _pad_rows(rows, rows_padded).bfloat16()
 
 
 # --------------------------------------------------------------------------

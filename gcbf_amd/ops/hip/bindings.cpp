@@ -96,7 +96,7 @@ extern "C" void launch_rollout_tail(
         long* edge_index, long* seg, float* edge_attr, int* flags, int N,
         int n, int n_rec, int S, int P, float dt, float r_agent, float sl,
         float d2g, float act_lim, float r_comm, int attr_kind, int A_attr,
-        long E_max, int threads, hipStream_t stream);
+        long E_max, int topk, int threads, hipStream_t stream);
 
 extern "C" int rollout_tail_batched_max_rows();
 extern "C" int rollout_tail_batched_max_nodes();
@@ -140,6 +140,10 @@ extern "C" void launch_rows_cat_pad_bf16(const void* a, const float* b,
                                          hipStream_t stream);
 extern "C" void launch_refresh_mirrors(const long long* table, int n_layers,
                                        long max_groups, hipStream_t stream);
+extern "C" void launch_segmax_rows_bf16(const void* msg, const long* seg,
+                                        const long* idx, void* out, int E,
+                                        int D, int n_rows, int num_nodes,
+                                        int rows, hipStream_t stream);
 
 namespace {
 
@@ -677,10 +681,13 @@ void rollout_tail(int64_t kind, torch::Tensor states, torch::Tensor goal,
                   double dt, double r, double sl, double d2g, double act_lim,
                   int64_t n_rec, double comm_radius, int64_t attr_kind,
                   int64_t attr_dim, int64_t E_max,
-                  std::vector<torch::Tensor> out, int64_t threads) {
+                  std::vector<torch::Tensor> out, int64_t threads,
+                  int64_t topk) {
     // kinds as in masks.hip: 0 car, 1 dubins, 2 drone
     TORCH_CHECK(kind >= 0 && kind <= 2, "rollout_tail: unknown env kind ",
                 kind);
+    TORCH_CHECK(topk == -1 || (topk >= 1 && topk < (int64_t(1) << 31)),
+                "rollout_tail: topk must be -1 (no cap) or >= 1, got ", topk);
     const int64_t S = kind == 2 ? 6 : 4, P = kind == 2 ? 3 : 2;
     const int64_t A = kind == 2 ? 3 : 2, G = kind == 0 ? 2 : S;
     TORCH_CHECK(states.dim() == 2 && action.dim() == 2,
@@ -745,7 +752,7 @@ void rollout_tail(int64_t kind, torch::Tensor states, torch::Tensor goal,
         edge_attr.data_ptr<float>(), flags.data_ptr<int>(), (int)N, (int)n,
         (int)n_rec, (int)S, (int)P, (float)dt, (float)r, (float)sl,
         (float)d2g, (float)act_lim, (float)comm_radius, (int)attr_kind,
-        (int)attr_dim, E_max, (int)threads, current_stream());
+        (int)attr_dim, E_max, (int)topk, (int)threads, current_stream());
 }
 
 // ---- batched rollout tail (rollout_tail_batched.hip): the same for B
@@ -1062,6 +1069,52 @@ torch::Tensor rows_cat_bwd(torch::Tensor din, int64_t Da, int64_t n_rows,
     return da;
 }
 
+// ---- MACBF actor glue (macbf_glue.hip): segment max of φ's padded bf16
+// output straight into γ's padded bf16 input.  Row r is the max over the
+// messages of node idx[r] (int64), or node r without an index; rows past
+// n_rows and empty segments are zero.  Forward only.
+torch::Tensor segmax_rows_bf16(torch::Tensor msg, torch::Tensor seg,
+                               c10::optional<torch::Tensor> idx,
+                               int64_t n_rows, int64_t num_nodes,
+                               int64_t rows_padded) {
+    CHECK_IN(msg); CHECK_IN(seg);
+    TORCH_CHECK(!torch::GradMode::is_enabled() || !msg.requires_grad(),
+                "segmax_rows_bf16 is forward only: call it without grad");
+    TORCH_CHECK(msg.scalar_type() == torch::kBFloat16 && msg.dim() == 2,
+                "msg must be bf16 (rows, D)");
+    TORCH_CHECK(seg.scalar_type() == torch::kInt64 && seg.dim() == 1,
+                "seg must be int64 (E,)");
+    TORCH_CHECK(seg.device() == msg.device(),
+                "segmax_rows_bf16: all tensors must be on one device");
+    const int64_t E = seg.size(0), D = msg.size(1);
+    TORCH_CHECK(msg.size(0) >= E, "msg must cover every edge slot");
+    TORCH_CHECK(n_rows >= 0 && n_rows <= rows_padded && num_nodes >= 0,
+                "segmax_rows_bf16: bad n_rows ", n_rows);
+    const int64_t* iptr = nullptr;
+    if (idx.has_value()) {
+        CHECK_IN(idx.value());
+        TORCH_CHECK(idx->scalar_type() == torch::kInt64 && idx->dim() == 1 &&
+                    idx->size(0) == n_rows &&
+                    idx->device() == msg.device(),
+                    "idx must be int64 (n_rows,) on msg's device");
+        iptr = idx->data_ptr<int64_t>();
+    } else {
+        TORCH_CHECK(n_rows <= num_nodes,
+                    "segmax_rows_bf16: n_rows above num_nodes");
+    }
+    TORCH_CHECK(E < (int64_t(1) << 31) && rows_padded < (int64_t(1) << 31) &&
+                num_nodes < (int64_t(1) << 31) && D < (int64_t(1) << 24) &&
+                E * D < (int64_t(1) << 40),
+                "segmax_rows_bf16: sizes out of range");
+    auto out = torch::empty({rows_padded, D}, msg.options());
+    if (out.numel() > 0)
+        launch_segmax_rows_bf16(msg.data_ptr(), seg.data_ptr<int64_t>(), iptr,
+                                out.data_ptr(), (int)E, (int)D, (int)n_rows,
+                                (int)num_nodes, (int)rows_padded,
+                                current_stream());
+    return out;
+}
+
 torch::Tensor rows_cat_pad_bf16(torch::Tensor a, torch::Tensor b,
                                 int64_t n_rows, int64_t rows_padded) {
     CHECK_IN(a); CHECK_IN(b);
@@ -1222,7 +1275,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("sl"), py::arg("d2g"), py::arg("act_lim"),
           py::arg("n_rec"), py::arg("comm_radius"), py::arg("attr_kind"),
           py::arg("attr_dim"), py::arg("E_max"), py::arg("out"),
-          py::arg("threads") = 1024);
+          py::arg("threads") = 1024, py::arg("topk") = -1);
     m.def("rollout_tail_bounds", &rollout_tail_bounds,
           "(max receiver rows, max nodes) the single-workgroup tail takes");
     m.def("edge_inputs_bf16", &edge_inputs_bf16,
@@ -1259,6 +1312,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[a_bf16, b_fp32] as zero-padded bf16 rows",
           py::arg("a"), py::arg("b"), py::arg("n_rows"),
           py::arg("rows_padded"));
+    m.def("segmax_rows_bf16", &segmax_rows_bf16,
+          "segment max of bf16 messages as zero-padded bf16 rows (no grad)",
+          py::arg("msg"), py::arg("seg"), py::arg("idx"), py::arg("n_rows"),
+          py::arg("num_nodes"), py::arg("rows_padded"));
     m.def("mirror_table", &mirror_table,
           "checked host table (n, 8) int64 for refresh_mirrors");
     m.def("refresh_mirrors", &refresh_mirrors,

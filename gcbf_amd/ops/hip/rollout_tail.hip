@@ -19,6 +19,9 @@
 // those map "one wave per row" over a grid, this kernel loops
 // ``for (row = wave; row < rows; row += n_waves)``.  No arithmetic is
 // re-derived here, so every output is bit-equal to the kernel sequence.
+// ``topk`` is the neighbour cap count_row / fill_row take (k nearest senders
+// per receiver, ties kept; -1: none); the cap's k-th-distance scan lives in
+// registers, so the LDS bound below does not depend on it.
 //
 // Barrier discipline: every __syncthreads() sits at the top level of the
 // kernel body, outside every loop and branch; there is no return before the
@@ -50,7 +53,7 @@ __global__ void __launch_bounds__(1024) rollout_tail_kernel(
         int* __restrict__ flags,              // (3,) out
         int N, int n, int n_rec, int S, int P, float dt, float r_agent,
         float sl, float d2g, float act_lim, float r_comm, int attr_kind,
-        int A_attr, long E_max) {
+        int A_attr, long E_max, int topk) {
     __shared__ int s_counts[TAIL_MAX_ROWS];
     __shared__ int s_offsets[TAIL_MAX_ROWS];
     __shared__ int s_unsafe[TAIL_MAX_WAVES];
@@ -100,7 +103,7 @@ __global__ void __launch_bounds__(1024) rollout_tail_kernel(
     // ---- C: per-receiver edge counts on the NEW states; positions are
     // the leading P columns of states_out (row stride S)
     for (int row = wave; row < n_rec; row += n_waves) {
-        const int cnt = count_row(states_out, P, S, 0, row, N, r_comm, -1,
+        const int cnt = count_row(states_out, P, S, 0, row, N, r_comm, topk,
                                   lane);
         if (lane == 0) s_counts[row] = cnt;
     }
@@ -128,7 +131,7 @@ __global__ void __launch_bounds__(1024) rollout_tail_kernel(
     // ---- D: ordered fill of edge_index / edge_attr
     for (int row = wave; row < n_rec; row += n_waves)
         fill_row(states_out, S, states_out, s_offsets[row], edge_index,
-                 edge_attr, E_max, 0, row, N, P, S, A_attr, r_comm, -1,
+                 edge_attr, E_max, 0, row, N, P, S, A_attr, r_comm, topk,
                  attr_kind, lane);
     __syncthreads();  // 4: real edges written (pad reads their dst row)
 
@@ -153,8 +156,9 @@ __global__ void __launch_bounds__(1024) rollout_tail_kernel(
 extern "C" int rollout_tail_max_rows() { return TAIL_MAX_ROWS; }
 extern "C" int rollout_tail_max_nodes() { return TAIL_MAX_NODES; }
 
-// kind: ENV_CAR / ENV_DUBINS / ENV_DRONE (masks_common.h); threads: 256,
-// 512 or 1024.  Grid is always one workgroup.
+// kind: ENV_CAR / ENV_DUBINS / ENV_DRONE (masks_common.h); topk: neighbour
+// cap of graph_build_common.h (-1: none); threads: 256, 512 or 1024.  Grid
+// is always one workgroup.
 extern "C" void launch_rollout_tail(
         int kind, const float* states_in, const float* goal,
         const float* action, const float* K, float* states_out,
@@ -162,14 +166,14 @@ extern "C" void launch_rollout_tail(
         long* edge_index, long* seg, float* edge_attr, int* flags, int N,
         int n, int n_rec, int S, int P, float dt, float r_agent, float sl,
         float d2g, float act_lim, float r_comm, int attr_kind, int A_attr,
-        long E_max, int threads, hipStream_t stream) {
+        long E_max, int topk, int threads, hipStream_t stream) {
 #define TAIL_LAUNCH(KIND)                                                  \
     hipLaunchKernelGGL(rollout_tail_kernel<KIND>, dim3(1), dim3(threads),  \
                        0, stream, states_in, goal, action, K, states_out,  \
                        u_ref_next, reward, reach, collision, edge_index,   \
                        seg, edge_attr, flags, N, n, n_rec, S, P, dt,       \
                        r_agent, sl, d2g, act_lim, r_comm, attr_kind,       \
-                       A_attr, E_max)
+                       A_attr, E_max, topk)
     if (kind == ENV_DUBINS) TAIL_LAUNCH(ENV_DUBINS);
     else if (kind == ENV_CAR) TAIL_LAUNCH(ENV_CAR);
     else TAIL_LAUNCH(ENV_DRONE);

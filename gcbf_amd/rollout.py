@@ -25,6 +25,11 @@ termination and replay-buffer appends stay on the host.
 
 Weights are read by address, so Adam steps between replays take effect
 without re-capture.
+
+GCBF on uncapped scenes by default; ``engine_supported(..., capped=True)``
+(``train.py --capture-capped``) also admits MACBF and neighbour-capped
+scenes: the env's ``max_neighbors`` becomes the builder's and the tail's
+``topk``, and the exploration draw honours ``algo.explore_prob``.
 """
 from __future__ import annotations
 
@@ -45,14 +50,20 @@ TAIL_MAX_ROWS = 32
 TAIL_MAX_NODES = 64
 
 
-def engine_supported(env, algo) -> bool:
+def engine_supported(env, algo, capped: bool = False) -> bool:
+    """Whether :class:`RolloutEngine` serves this env and algorithm.
+    ``capped`` (opt-in) also admits MACBF and neighbour-capped scenes
+    (``max_neighbors``)."""
     from .algo.gcbf import GCBF
     from .algo.macbf import MACBF
     if not torch.cuda.is_available() or not ops.hip_available():
         return False
-    if not isinstance(algo, GCBF) or isinstance(algo, MACBF):
+    if not isinstance(algo, GCBF):
         return False
-    if env._mode != "train" or env._max_neighbors is not None:
+    if not capped and (isinstance(algo, MACBF)
+                       or env._max_neighbors is not None):
+        return False
+    if env._mode != "train":
         return False
     data = env.data if env.data is not None else env.reset()
     n, N = env.num_agents, data.num_nodes
@@ -122,8 +133,11 @@ class RolloutEngine:
         # GCBF_AMD_ROLLOUT_TAIL=0 keeps the multi-kernel body (read here, at
         # construction, so one process can build both kinds of engine)
         self.n_rec = self.n if self.agent_mask is not None else self.N
+        # neighbour cap of the scene's graphs (the env's max_neighbors),
+        # read once: -1 is no cap
+        self.topk = (-1 if env._max_neighbors is None
+                     else int(env._max_neighbors))
         self._tail = (os.environ.get("GCBF_AMD_ROLLOUT_TAIL", "1") != "0"
-                      and env._max_neighbors is None
                       and self.n_rec <= TAIL_MAX_ROWS
                       and self.N <= TAIL_MAX_NODES
                       and ops.rollout_tail_supported(self.n_rec, self.N))
@@ -138,7 +152,11 @@ class RolloutEngine:
         # attach the ring store up front so per-step snapshots can be
         # metadata-only from the first step (GCBF builds it lazily at the
         # first update otherwise)
+        # (not for MACBF: its update batches the stored graphs themselves,
+        # which a metadata-only snapshot does not carry)
+        from .algo.macbf import MACBF
         if getattr(algo, "_ring", None) is None \
+                and not isinstance(algo, MACBF) \
                 and hasattr(algo, "_make_ring") \
                 and not getattr(algo, "_ring_tried", True):
             algo._make_ring()
@@ -170,7 +188,8 @@ class RolloutEngine:
                     self.env._attr_kind, self.edge_dim, self.E_max,
                     out=[self.states[o], self.u_ref[o], self.reward_buf,
                          self.reach_buf, self.coll_buf, self.ei[o],
-                         self.seg[o], self.ea[o], self.flags])
+                         self.seg[o], self.ea[o], self.flags],
+                    topk=self.topk)
                 return
             unsafe_any = self.env.unsafe_mask(data).any()
             # kernels write set o directly (out= buffers), so the replay
@@ -184,7 +203,7 @@ class RolloutEngine:
                 self.states[o][:, :self.pos_dim].contiguous(),
                 self.states[o], 1,
                 self.n if self.agent_mask is not None else self.N,
-                self.env.params["comm_radius"], -1,
+                self.env.params["comm_radius"], self.topk,
                 self.env._attr_kind, self.edge_dim, self.E_max,
                 out=[self.ei[o], self.seg[o], self.ea[o], self.flags[0:1]])
             self.flags[1].copy_(self.reach_buf.all().to(torch.int32))
@@ -237,7 +256,7 @@ class RolloutEngine:
         ei, seg, ea, ecount = self._ext.build_graph_padded(
             data.pos.contiguous(), data.states.contiguous(), 1,
             self.n if self.agent_mask is not None else self.N,
-            self.env.params["comm_radius"], -1,
+            self.env.params["comm_radius"], self.topk,
             self.env._attr_kind, self.edge_dim, self.E_max)
         self.ei[c].copy_(ei)
         self.seg[c].copy_(seg)
@@ -312,7 +331,11 @@ class RolloutEngine:
                 agent_mask=self.agent_mask,
                 u_ref=self.u_ref[c].clone())
 
-        self.g[(np.random.rand() < prob, c)].replay()
+        # one draw per step, against the probability algo.step would use
+        # (MACBF floors it), so this loop and the eager one consume the
+        # same random stream
+        explore = np.random.rand() < self.algo.explore_prob(prob)
+        self.g[(explore, c)].replay()
         self.cur = c = 1 - c
 
         flags = self.flags.cpu()  # ONE host sync per step

@@ -27,7 +27,7 @@ class Trainer:
     def __init__(self, env: MultiAgentEnv, env_test: MultiAgentEnv,
                  algo: Algorithm, log_dir: str, rank: int = 0,
                  world_size: int = 1, eval_batch: bool = False,
-                 num_envs: int = 1):
+                 num_envs: int = 1, capture_capped: bool = False):
         self.env = env
         self.env_test = env_test
         self.algo = algo
@@ -36,6 +36,10 @@ class Trainer:
         self.world_size = world_size
         # opt-in: run the eval episodes as one SceneBatch
         self.eval_batch = eval_batch
+        # opt-in: let the captured rollout engine take MACBF and
+        # neighbour-capped scenes too (gcbf_amd/rollout.py); off keeps
+        # their eager loop
+        self.capture_capped = bool(capture_capped)
         # opt-in: collect from num_envs scenes per captured step
         # (gcbf_amd/vec_rollout.py); 1 keeps the single-scene loop
         self.num_envs = int(num_envs)
@@ -63,10 +67,12 @@ class Trainer:
             self.writer = NullWriter()
 
     def _make_engine(self):
-        """hipGraph-captured rollout when supported (GPU + HIP ext + GCBF)."""
+        """hipGraph-captured rollout when supported (GPU + HIP ext + GCBF;
+        with ``capture_capped`` also MACBF and neighbour-capped scenes)."""
         try:
             from ..rollout import RolloutEngine, engine_supported
-            if engine_supported(self.env, self.algo):
+            if engine_supported(self.env, self.algo,
+                                capped=self.capture_capped):
                 if self.env.data is None:
                     self.env.reset()
                 return RolloutEngine(self.env, self.algo)

@@ -98,7 +98,8 @@ def train(args):
 
     trainer = Trainer(env=env, env_test=env_test, algo=algo, log_dir=log_path,
                       rank=rank, world_size=world_size,
-                      eval_batch=args.eval_batch, num_envs=args.num_envs)
+                      eval_batch=args.eval_batch, num_envs=args.num_envs,
+                      capture_capped=args.capture_capped)
     start_step = 1
     if args.resume is not None:
         model_dir = os.path.join(log_path, "models")
@@ -149,4 +150,11 @@ if __name__ == "__main__":
                         help="collect from this many independent scenes per "
                              "captured rollout step (--batch-size must be a "
                              "multiple of it; 1: the single-scene engine)")
+    parser.add_argument("--capture-capped", action="store_true",
+                        default=os.environ.get(
+                            "GCBF_AMD_CAPTURE_CAPPED", "0") == "1",
+                        help="collect MACBF / neighbour-capped rollouts with "
+                             "the captured engine too (also "
+                             "GCBF_AMD_CAPTURE_CAPPED=1; default: their "
+                             "eager loop)")
     train(parser.parse_args())
