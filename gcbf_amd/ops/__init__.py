@@ -378,7 +378,8 @@ def rollout_tail_batched_supported(B: int, n_rec: int,
 
 def rollout_tail_batched(step_args, explore: Tensor, n_rec: int,
                          comm_radius: float, attr_kind: int, attr_dim: int,
-                         E_cap: int, out, threads: int = 1024) -> None:
+                         E_cap: int, out, threads: int = 1024,
+                         topk: int = -1) -> None:
     """:func:`rollout_tail` for ``B`` scenes of one static layout, in two
     launches of ``B`` workgroups (rollout_tail_batched.hip).  On ``states``
     (B, N, S), ``goal`` (B, n, G), ``action`` (B, n, A) and ``explore``
@@ -389,8 +390,13 @@ def rollout_tail_batched(step_args, explore: Tensor, n_rec: int,
         env_step_batched(kind, states, goal, where(explore, 0, action),
                          active=ones(B), ...)
         _C.build_graph_padded(new_states[..., :pos_dim], new_states, B,
-                              n_rec, comm_radius, -1, attr_kind, attr_dim,
+                              n_rec, comm_radius, topk, attr_kind, attr_dim,
                               E_cap)
+
+    ``topk`` caps every receiver at its k nearest senders of its own scene,
+    ties at the k-th distance kept (the env's ``max_neighbors``); -1 is no
+    cap.  Each row's cap threshold is searched for once, in the first launch,
+    and handed to the second.
 
     ``step_args`` is ``env.fused_step_args(...)`` on the batched tensors.
     ``out`` is [new_states, u_ref_next, reward (B, n), reach, collision,
@@ -411,7 +417,7 @@ def rollout_tail_batched(step_args, explore: Tensor, n_rec: int,
     ext.rollout_tail_batched(
         _TAIL_KIND[kind], states, goal, action, explore, K, dt, r, sl, d2g,
         act_lim, n_rec, float(comm_radius), int(attr_kind), int(attr_dim),
-        int(E_cap), list(out), threads)
+        int(E_cap), list(out), threads, topk=int(topk))
 
 
 # --------------------------------------------------------------------------

@@ -105,11 +105,11 @@ extern "C" void launch_rollout_tail_batched(
         int kind, const float* states_in, const float* goal,
         const float* action, const int* explore, const float* K,
         float* states_out, float* u_ref_next, float* reward, bool* reach,
-        bool* collision, int* counts, long* edge_index, long* seg,
+        bool* collision, int* counts, float* thr, long* edge_index, long* seg,
         float* edge_attr, int* flags, int* e_count, int B, int N, int n,
         int n_rec, int S, int G, int A, int P, float dt, float r_agent,
         float sl, float d2g, float act_lim, float r_comm, int attr_kind,
-        int A_attr, long E_cap, int threads, hipStream_t stream);
+        int A_attr, long E_cap, int topk, int threads, hipStream_t stream);
 
 extern "C" void launch_edge_inputs_bf16(const float* x, const long* ei,
                                         const float* ea, void* out, int N,
@@ -769,9 +769,12 @@ void rollout_tail_batched(
         c10::optional<torch::Tensor> K, double dt, double r, double sl,
         double d2g, double act_lim, int64_t n_rec, double comm_radius,
         int64_t attr_kind, int64_t attr_dim, int64_t E_cap,
-        std::vector<torch::Tensor> out, int64_t threads) {
+        std::vector<torch::Tensor> out, int64_t threads, int64_t topk) {
     TORCH_CHECK(kind >= 0 && kind <= 2,
                 "rollout_tail_batched: unknown env kind ", kind);
+    TORCH_CHECK(topk == -1 || (topk >= 1 && topk < (int64_t(1) << 31)),
+                "rollout_tail_batched: topk must be -1 (no cap) or >= 1, "
+                "got ", topk);
     const int64_t S = kind == 2 ? 6 : 4, P = kind == 2 ? 3 : 2;
     const int64_t A = kind == 2 ? 3 : 2, G = kind == 0 ? 2 : S;
     TORCH_CHECK(states.dim() == 3 && action.dim() == 3,
@@ -855,18 +858,25 @@ void rollout_tail_batched(
     // per-row counts: the hand-over between the two launches
     auto counts = torch::empty({B * n_rec},
                                states.options().dtype(torch::kInt32));
+    // per-row cap thresholds, the same hand-over; only while the cap is live
+    float* thr_ptr = nullptr;
+    torch::Tensor thr;
+    if (topk > 0 && topk < N) {
+        thr = torch::empty({B * n_rec}, states.options());
+        thr_ptr = thr.data_ptr<float>();
+    }
     launch_rollout_tail_batched(
         (int)kind, states.data_ptr<float>(), goal.data_ptr<float>(),
         action.data_ptr<float>(), explore.data_ptr<int>(), kptr,
         new_states.data_ptr<float>(), u_ref_next.data_ptr<float>(),
         reward.data_ptr<float>(), reach.data_ptr<bool>(),
-        collision.data_ptr<bool>(), counts.data_ptr<int>(),
+        collision.data_ptr<bool>(), counts.data_ptr<int>(), thr_ptr,
         edge_index.data_ptr<int64_t>(), seg.data_ptr<int64_t>(),
         edge_attr.data_ptr<float>(), flags.data_ptr<int>(),
         e_count.data_ptr<int>(), (int)B, (int)N, (int)n, (int)n_rec, (int)S,
         (int)G, (int)A, (int)P, (float)dt, (float)r, (float)sl, (float)d2g,
         (float)act_lim, (float)comm_radius, (int)attr_kind, (int)attr_dim,
-        E_cap, (int)threads, current_stream());
+        E_cap, (int)topk, (int)threads, current_stream());
 }
 
 // ---- MLP glue (mlp_glue.hip): padded bf16 GEMM inputs written directly
@@ -1265,7 +1275,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dt"), py::arg("r"), py::arg("sl"), py::arg("d2g"),
           py::arg("act_lim"), py::arg("n_rec"), py::arg("comm_radius"),
           py::arg("attr_kind"), py::arg("attr_dim"), py::arg("E_cap"),
-          py::arg("out"), py::arg("threads") = 1024);
+          py::arg("out"), py::arg("threads") = 1024, py::arg("topk") = -1);
     m.def("rollout_tail_batched_bounds", &rollout_tail_batched_bounds,
           "(max scenes, max receiver rows, max nodes per scene)");
     m.def("rollout_tail", &rollout_tail,

@@ -75,19 +75,28 @@ __device__ __forceinline__ float row_kth(const float* pos, int P, int stride,
     return kth;
 }
 
-// edge count of receiver row i (wave-uniform)
-__device__ __forceinline__ int count_row(const float* pos, int P, int stride,
-                                         int gbase, int i, int N, float r,
-                                         int topk, int lane) {
+// edge count of receiver row i under a given cap threshold ``kth`` (from
+// row_kth; wave-uniform)
+__device__ __forceinline__ int count_row_thr(const float* pos, int P,
+                                             int stride, int gbase, int i,
+                                             int N, float r, float kth,
+                                             int lane) {
     const float big = r + 1.f;
-    const float kth = row_kth(pos, P, stride, gbase, i, N, big, topk, lane);
-
     int cnt = 0;
     for (int j = lane; j < N; j += WAVE) {
         const float d = row_dist(pos, P, stride, gbase, i, j, big);
         cnt += (d < r && d <= kth);
     }
     return wave_sum_i(cnt);
+}
+
+// edge count of receiver row i (wave-uniform)
+__device__ __forceinline__ int count_row(const float* pos, int P, int stride,
+                                         int gbase, int i, int N, float r,
+                                         int topk, int lane) {
+    const float kth = row_kth(pos, P, stride, gbase, i, N, r + 1.f, topk,
+                              lane);
+    return count_row_thr(pos, P, stride, gbase, i, N, r, kth, lane);
 }
 
 // edge_attr kinds
@@ -111,14 +120,15 @@ __device__ __forceinline__ void write_attr(float* attr, const float* states,
 }
 
 // ordered, ballot-compacted fill of receiver row i starting at edge ``base``
-__device__ __forceinline__ void fill_row(const float* pos, int stride,
-                                         const float* states, int base,
-                                         long* edge_index, float* edge_attr,
-                                         long E_total, int gbase, int i,
-                                         int N, int P, int S, int A, float r,
-                                         int topk, int attr_kind, int lane) {
+// under a given cap threshold ``kth`` (from row_kth)
+__device__ __forceinline__ void fill_row_thr(const float* pos, int stride,
+                                             const float* states, int base,
+                                             long* edge_index,
+                                             float* edge_attr, long E_total,
+                                             int gbase, int i, int N, int P,
+                                             int S, int A, float r, float kth,
+                                             int attr_kind, int lane) {
     const float big = r + 1.f;
-    const float kth = row_kth(pos, P, stride, gbase, i, N, big, topk, lane);
 
     for (int j0 = 0; j0 < N; j0 += WAVE) {
         const int j = j0 + lane;
@@ -144,6 +154,19 @@ __device__ __forceinline__ void fill_row(const float* pos, int stride,
         }
         base += __popcll(mask);
     }
+}
+
+// ordered, ballot-compacted fill of receiver row i starting at edge ``base``
+__device__ __forceinline__ void fill_row(const float* pos, int stride,
+                                         const float* states, int base,
+                                         long* edge_index, float* edge_attr,
+                                         long E_total, int gbase, int i,
+                                         int N, int P, int S, int A, float r,
+                                         int topk, int attr_kind, int lane) {
+    const float kth = row_kth(pos, P, stride, gbase, i, N, r + 1.f, topk,
+                              lane);
+    fill_row_thr(pos, stride, states, base, edge_index, edge_attr, E_total,
+                 gbase, i, N, P, S, A, r, kth, attr_kind, lane);
 }
 
 // entry idx < E_max of the padded edge list holding E real edges: real

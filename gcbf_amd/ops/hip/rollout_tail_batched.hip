@@ -9,8 +9,10 @@
 //   B  env step     <env>_step_row  (env_step_common.h)     states_in -> out
 //   -- barrier: this workgroup's global writes of states_out become visible
 //      to this workgroup (same-workgroup RAW, as rollout_tail.hip relies on)
-//   C  count        count_row       (graph_build_common.h)  on states_out,
-//      gbase = b*N, into counts[b*n_rec + row]
+//   C  count        row_kth + count_row_thr (graph_build_common.h) on
+//      states_out, gbase = b*N, into counts[b*n_rec + row]; with a live
+//      neighbour cap (0 < topk < N) the row's threshold goes to
+//      thr[b*n_rec + row]
 //   -- barrier
 //   F  flags[b] = {scene_edge_count, all(reach), unsafe_any}  (one lane)
 //
@@ -19,19 +21,22 @@
 //           scenes (B <= 64: one wave trip); exclusive scan of the scene's
 //           row counts into LDS
 //   -- barrier
-//   D  fill         fill_row  from base_b + offset[row] into the ONE
+//   D  fill         fill_row_thr  from base_b + offset[row] into the ONE
 //      globally compacted padded edge list (all pads after all real edges,
-//      which the CSR consumers' searchsorted over seg needs)
+//      which the CSR consumers' searchsorted over seg needs); the cap
+//      threshold is read back from thr, not searched for again
 //   -- barrier: seg reads the dst row that this workgroup's fill wrote
 //   E  seg of this scene's real edges; the pad range [E, E_cap) is split
 //      evenly over the B workgroups (pad_entry)
 //   workgroup 0 publishes E to e_count
 //
-// The hand-over between the two kernels (states_out, counts, flags) goes
-// through global memory and stream order only.  The per-wave bodies are the
+// The hand-over between the two kernels (states_out, counts, thr, flags)
+// goes through global memory and stream order only.  thr is touched only
+// while the cap is live; without one (topk = -1, or topk >= N) both kernels
+// use FLT_MAX and the pointer may be null.  The per-wave bodies are the
 // ones the stand-alone kernels call; no arithmetic is re-derived here, so
 // every output is bit-equal to the kernel sequence
-//   fused_masks -> env_step_batched -> build_graph_padded(batch=B).
+//   fused_masks -> env_step_batched -> build_graph_padded(batch=B, topk).
 //
 // Barrier discipline as in rollout_tail.hip: every __syncthreads() sits at
 // the top level of the kernel body, outside every loop and branch; there is
@@ -61,9 +66,11 @@ __global__ void __launch_bounds__(1024) tail_batched_step(
         float* __restrict__ u_ref_next, float* __restrict__ reward,
         bool* __restrict__ reach, bool* __restrict__ collision,
         int* __restrict__ counts,             // (B*n_rec,) out
+        float* __restrict__ thr,              // (B*n_rec,) out, cap live only
         int* __restrict__ flags,              // (B, 3) out
         int N, int n, int n_rec, int S, int G, int A, int P, float dt,
-        float r_agent, float sl, float d2g, float act_lim, float r_comm) {
+        float r_agent, float sl, float d2g, float act_lim, float r_comm,
+        int topk) {
     __shared__ float s_action[TB_MAX_NODES * TB_MAX_ACT];
     __shared__ int s_counts[TB_MAX_ROWS];
     __shared__ int s_unsafe[TB_MAX_WAVES];
@@ -128,14 +135,20 @@ __global__ void __launch_bounds__(1024) tail_batched_step(
     __syncthreads();  // 1: states_out written, per-wave flags in LDS
 
     // ---- C: per-receiver edge counts on the NEW states; positions are the
-    // leading P columns of states_out (row stride S), rows of scene b
+    // leading P columns of states_out (row stride S), rows of scene b.  The
+    // cap threshold (up to 2k sweeps of the row) is found here once and
+    // handed to the fill kernel
     const int gbase = (int)b * N;
+    const bool capped = topk > 0 && topk < N;
     for (int row = wave; row < n_rec; row += n_waves) {
-        const int cnt = count_row(states_out, P, S, gbase, row, N, r_comm,
-                                  -1, lane);
+        const float kth = row_kth(states_out, P, S, gbase, row, N,
+                                  r_comm + 1.f, topk, lane);
+        const int cnt = count_row_thr(states_out, P, S, gbase, row, N,
+                                      r_comm, kth, lane);
         if (lane == 0) {
             s_counts[row] = cnt;
             counts[b * (size_t)n_rec + row] = cnt;
+            if (capped) thr[b * (size_t)n_rec + row] = kth;
         }
     }
     __syncthreads();  // 2: counts in LDS
@@ -161,13 +174,14 @@ __global__ void __launch_bounds__(1024) tail_batched_step(
 __global__ void __launch_bounds__(1024) tail_batched_fill(
         const float* states_out,              // (B, N, S) new states
         const int* __restrict__ counts,       // (B*n_rec,)
+        const float* __restrict__ thr,        // (B*n_rec,), cap live only
         const int* __restrict__ flags,        // (B, 3)
         long* edge_index,                     // (2, E_cap) out
         long* seg,                            // (E_cap,) out
         float* edge_attr,                     // (E_cap, A_attr) out
         int* __restrict__ e_count,            // (1,) out
-        int B, int N, int n_rec, int S, int P, float r_comm, int attr_kind,
-        int A_attr, long E_cap) {
+        int B, int N, int n_rec, int S, int P, float r_comm, int topk,
+        int attr_kind, int A_attr, long E_cap) {
     __shared__ int s_offsets[TB_MAX_ROWS];
     __shared__ int s_base;
     __shared__ int s_scene;
@@ -208,10 +222,13 @@ __global__ void __launch_bounds__(1024) tail_batched_fill(
 
     // ---- D: ordered fill of this scene's edges at base_b + offset[row]
     const int base_b = s_base;
-    for (int row = wave; row < n_rec; row += n_waves)
-        fill_row(states_out, S, states_out, base_b + s_offsets[row],
-                 edge_index, edge_attr, E_cap, b * N, row, N, P, S, A_attr,
-                 r_comm, -1, attr_kind, lane);
+    const bool capped = topk > 0 && topk < N;
+    for (int row = wave; row < n_rec; row += n_waves) {
+        const float kth = capped ? thr[(size_t)b * n_rec + row] : FLT_MAX;
+        fill_row_thr(states_out, S, states_out, base_b + s_offsets[row],
+                     edge_index, edge_attr, E_cap, b * N, row, N, P, S,
+                     A_attr, r_comm, kth, attr_kind, lane);
+    }
     __syncthreads();  // 2: real edges written (seg reads their dst row)
 
     // ---- E: seg ids of this scene's real edges
@@ -240,28 +257,29 @@ extern "C" int rollout_tail_batched_max_nodes() { return TB_MAX_NODES; }
 extern "C" int rollout_tail_batched_max_scenes() { return TB_MAX_SCENES; }
 
 // kind: ENV_CAR / ENV_DUBINS / ENV_DRONE (masks_common.h); threads: 256,
-// 512 or 1024.  Both grids are B workgroups.
+// 512 or 1024.  Both grids are B workgroups.  topk: neighbour cap, -1 none;
+// thr: (B*n_rec,) workspace, needed only where 0 < topk < N.
 extern "C" void launch_rollout_tail_batched(
         int kind, const float* states_in, const float* goal,
         const float* action, const int* explore, const float* K,
         float* states_out, float* u_ref_next, float* reward, bool* reach,
-        bool* collision, int* counts, long* edge_index, long* seg,
+        bool* collision, int* counts, float* thr, long* edge_index, long* seg,
         float* edge_attr, int* flags, int* e_count, int B, int N, int n,
         int n_rec, int S, int G, int A, int P, float dt, float r_agent,
         float sl, float d2g, float act_lim, float r_comm, int attr_kind,
-        int A_attr, long E_cap, int threads, hipStream_t stream) {
+        int A_attr, long E_cap, int topk, int threads, hipStream_t stream) {
 #define TB_LAUNCH(KIND)                                                    \
     hipLaunchKernelGGL(tail_batched_step<KIND>, dim3(B), dim3(threads), 0, \
                        stream, states_in, goal, action, explore, K,        \
                        states_out, u_ref_next, reward, reach, collision,   \
-                       counts, flags, N, n, n_rec, S, G, A, P, dt,         \
-                       r_agent, sl, d2g, act_lim, r_comm)
+                       counts, thr, flags, N, n, n_rec, S, G, A, P, dt,    \
+                       r_agent, sl, d2g, act_lim, r_comm, topk)
     if (kind == ENV_DUBINS) TB_LAUNCH(ENV_DUBINS);
     else if (kind == ENV_CAR) TB_LAUNCH(ENV_CAR);
     else TB_LAUNCH(ENV_DRONE);
 #undef TB_LAUNCH
     hipLaunchKernelGGL(tail_batched_fill, dim3(B), dim3(threads), 0, stream,
-                       states_out, counts, flags, edge_index, seg, edge_attr,
-                       e_count, B, N, n_rec, S, P, r_comm, attr_kind, A_attr,
-                       E_cap);
+                       states_out, counts, thr, flags, edge_index, seg,
+                       edge_attr, e_count, B, N, n_rec, S, P, r_comm, topk,
+                       attr_kind, A_attr, E_cap);
 }

@@ -36,9 +36,9 @@ class Trainer:
         self.world_size = world_size
         # opt-in: run the eval episodes as one SceneBatch
         self.eval_batch = eval_batch
-        # opt-in: let the captured rollout engine take MACBF and
-        # neighbour-capped scenes too (gcbf_amd/rollout.py); off keeps
-        # their eager loop
+        # opt-in: let the captured rollout engines (gcbf_amd/rollout.py,
+        # and with num_envs > 1 gcbf_amd/vec_rollout.py) take MACBF and
+        # neighbour-capped scenes too; off keeps their eager loop
         self.capture_capped = bool(capture_capped)
         # opt-in: collect from num_envs scenes per captured step
         # (gcbf_amd/vec_rollout.py); 1 keeps the single-scene loop
@@ -155,16 +155,18 @@ class Trainer:
     # ------------------------------------------------- vectorized collection
     def _make_vec_engine(self):
         """The B-scene engine, or None (with the reason printed) where it
-        does not apply: the single-scene path then runs as always."""
+        does not apply: the single-scene path then runs as always.  MACBF
+        and neighbour-capped scenes need ``capture_capped`` here too."""
         from ..vec_rollout import (VecRolloutEngine,
                                    vec_engine_unsupported_reason)
         if self.env.data is None:
             self.env.reset()
-        reason = vec_engine_unsupported_reason(self.env, self.algo,
-                                               self.num_envs)
+        reason = vec_engine_unsupported_reason(
+            self.env, self.algo, self.num_envs, capped=self.capture_capped)
         if reason is None:
             try:
-                return VecRolloutEngine(self.env, self.algo, self.num_envs)
+                return VecRolloutEngine(self.env, self.algo, self.num_envs,
+                                        capped=self.capture_capped)
             except Exception as e:
                 reason = str(e)
         if self.rank == 0:

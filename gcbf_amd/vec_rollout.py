@@ -21,7 +21,7 @@ Two bodies share the bookkeeping.  The captured one uses the op above.  The
 plain one is the kernel sequence the op equals bit for bit
 
     fused_masks → env_step_batched(where(explore, 0, action)) →
-    build_graph_padded(batch=B)
+    build_graph_padded(batch=B, topk)
 
 with the eager implementations on CPU; it runs uncaptured, on CPU, with
 ``GCBF_AMD_VEC_TAIL=0`` and where the op's bounds do not hold.
@@ -34,6 +34,13 @@ lists; ``flush()`` appends them to ``algo.buffer`` scene by scene, each
 scene's steps in time order, so ``Buffer.sample``'s windows of consecutive
 graphs stay within one trajectory stream.  The env object serves as the
 scene generator: after a reset it holds the scene drawn last.
+
+GCBF on uncapped scenes by default; ``capped=True`` (``train.py --num-envs B
+--capture-capped``) also admits MACBF and neighbour-capped scenes, as
+``RolloutEngine`` does: the env's ``max_neighbors`` becomes the ``topk`` of
+the tail op and of every builder call, the exploration draw honours
+``algo.explore_prob``, and MACBF (whose update batches the stored graphs
+themselves) gets full-tensor snapshots, never ring slots.
 """
 from __future__ import annotations
 
@@ -50,20 +57,23 @@ from .graph import GraphBatch
 MAX_EDGE_CAPACITY = 262144
 
 
-def vec_engine_unsupported_reason(env, algo, B: int):
-    """None where ``VecRolloutEngine(env, algo, B)`` applies, else why not."""
+def vec_engine_unsupported_reason(env, algo, B: int, capped: bool = False):
+    """None where ``VecRolloutEngine(env, algo, B, capped)`` applies, else
+    why not.  ``capped`` (opt-in) also admits MACBF and neighbour-capped
+    scenes (``max_neighbors``)."""
     from .algo.gcbf import GCBF
     from .algo.macbf import MACBF
     from .env.point_agent import PointAgentEnv
     if B < 1:
         return "needs at least one scene"
-    if not isinstance(algo, GCBF) or isinstance(algo, MACBF):
+    if not isinstance(algo, GCBF) \
+            or (isinstance(algo, MACBF) and not capped):
         return "only GCBF collects vectorized (MACBF is out of scope)"
     if not isinstance(env, PointAgentEnv):
         return "needs a point-agent env"
     if env._mode != "train":
         return f"env mode {env._mode!r} is not 'train'"
-    if env._max_neighbors is not None:
+    if not capped and env._max_neighbors is not None:
         return "neighbour-capped scenes are not supported"
     if env.device.type == "cuda" and not ops.hip_available():
         return "the HIP extension is not built"
@@ -75,14 +85,14 @@ def vec_engine_unsupported_reason(env, algo, B: int):
     return None
 
 
-def vec_engine_supported(env, algo, B: int) -> bool:
-    return vec_engine_unsupported_reason(env, algo, B) is None
+def vec_engine_supported(env, algo, B: int, capped: bool = False) -> bool:
+    return vec_engine_unsupported_reason(env, algo, B, capped) is None
 
 
 class VecRolloutEngine:
 
-    def __init__(self, env, algo, B: int):
-        reason = vec_engine_unsupported_reason(env, algo, B)
+    def __init__(self, env, algo, B: int, capped: bool = False):
+        reason = vec_engine_unsupported_reason(env, algo, B, capped)
         if reason is not None:
             raise NotImplementedError(f"VecRolloutEngine: {reason}")
         self.env = env
@@ -97,7 +107,13 @@ class VecRolloutEngine:
         data = env.data if env.data is not None else env.reset()
         self.N = N = data.num_nodes
         S, A = env.state_dim, env.action_dim
+        # full capacity with or without a cap: ties at the k-th distance
+        # are all kept, so a capped row can exceed k
         self.E_cap = B * n * (N - 1)
+        # neighbour cap of the scenes' graphs (the env's max_neighbors),
+        # read once: -1 is no cap
+        self.topk = (-1 if env._max_neighbors is None
+                     else int(env._max_neighbors))
 
         # one scene's static content (snapshots share it)
         self.x1 = data.x.clone()
@@ -174,7 +190,11 @@ class VecRolloutEngine:
         self.g = None
         if self._tail:
             self._capture()
+        # (no ring for MACBF: its update batches the stored graphs
+        # themselves, which a metadata-only snapshot does not carry)
+        from .algo.macbf import MACBF
         if getattr(algo, "_ring", None) is None \
+                and not isinstance(algo, MACBF) \
                 and hasattr(algo, "_make_ring") \
                 and not getattr(algo, "_ring_tried", True):
             algo._make_ring()
@@ -205,13 +225,14 @@ class VecRolloutEngine:
         if self.cuda:
             self._ext.build_graph_padded(
                 flat[:, :pd].contiguous(), flat, B, self.n_rec,
-                self.env.params["comm_radius"], -1, self.env._attr_kind,
-                self.edge_dim, self.E_cap,
+                self.env.params["comm_radius"], self.topk,
+                self.env._attr_kind, self.edge_dim, self.E_cap,
                 out=[self.ei[i], self.seg[i], self.ea[i], self.e_count])
             return self._scene_counts(self.seg[i])
         ei, ea = ops.build_graph(
             flat[:, :pd], flat, None if self.am1 is None else self.n,
-            self.env.params["comm_radius"], None, B, self.env._attr_kind,
+            self.env.params["comm_radius"],
+            None if self.topk < 0 else self.topk, B, self.env._attr_kind,
             self.edge_dim, self.env.edge_attr)
         E = ei.shape[1]
         self.ei[i].zero_()
@@ -272,7 +293,8 @@ class VecRolloutEngine:
                 self.env._attr_kind, self.edge_dim, self.E_cap,
                 out=[self.states[o], self.u_ref[o], self.reward_buf,
                      self.reach_buf, self.coll_buf, self.ei[o], self.seg[o],
-                     self.ea[o], self.flags, self.e_count])
+                     self.ea[o], self.flags, self.e_count],
+                topk=self.topk)
 
     def _body_plain(self, all_explore: bool, i: int):
         """The sequence the tail op equals, call by call."""
@@ -376,8 +398,9 @@ class VecRolloutEngine:
         c = self.cur
         snaps = self._snapshots(c)
 
-        # exploration gate: one draw per scene
-        explore = np.random.rand(B) < prob
+        # exploration gate: one draw per scene, against the probability
+        # algo.step would use (MACBF floors it)
+        explore = np.random.rand(B) < self.algo.explore_prob(prob)
         all_explore = bool(explore.all())
         self.last_explore = explore
         self._explore_host.copy_(torch.from_numpy(explore.astype(np.int32)))

@@ -4,6 +4,8 @@
                                       [--envs 1 4 16] [--rounds 3]
                                       [--rollout-steps 1024]
                                       [--train-steps 1024] [--batch-size 512]
+                                      [--algo {gcbf,macbf}]
+                                      [--max-neighbors K] [--eager]
 
 Two figures per engine, on one process and one set of weights:
 
@@ -17,6 +19,12 @@ measures the baseline and then each ``VecRolloutEngine(B)``, so the
 ``--rounds`` samples of each configuration alternate in time with the
 baseline's.  The ranges (min..max over the rounds) are printed, and a gain
 is claimed for a B only where its range lies wholly above the baseline's.
+
+``--algo macbf`` and ``--max-neighbors K`` measure the opt-in capped path:
+every engine is built with ``capped=True`` and the baseline is the
+single-scene captured engine on the same capped scenes.  ``--eager`` adds the
+plain ``algo.step`` + ``env.step`` loop as a further row, and
+``--train-steps 0`` leaves the whole-training figure out.
 """
 import argparse
 import json
@@ -30,7 +38,7 @@ import torch
 
 from gcbf_amd.algo import make_algo
 from gcbf_amd.env import make_env
-from gcbf_amd.rollout import RolloutEngine
+from gcbf_amd.rollout import RolloutEngine, engine_supported
 from gcbf_amd.trainer.utils import set_seed
 from gcbf_amd.utils.amp import enable_bf16
 from gcbf_amd.vec_rollout import VecRolloutEngine
@@ -40,12 +48,38 @@ class _Single:
     """RolloutEngine behind the vectorized engine's interface."""
     B = 1
 
-    def __init__(self, env, algo):
+    def __init__(self, env, algo, capped=False):
+        assert engine_supported(env, algo, capped=capped)
         self.eng = RolloutEngine(env, algo)
 
     def step(self, prob):
         if self.eng.step(prob=prob):
             self.eng.reload()
+
+    def flush(self):
+        pass
+
+
+class _Eager:
+    """The trainer's plain single-scene loop behind the same interface."""
+    B = 1
+
+    def __init__(self, env, algo):
+        self.env, self.algo = env, algo
+        self.data = env.reset()
+
+    def step(self, prob):
+        env = self.env
+        if env.data is not self.data:   # another engine used the env since
+            self.data = env.reset()
+        data = self.data
+        if data.u_ref is None:
+            data.update(u_ref=env.u_ref(data))
+        action = self.algo.step(data, prob=prob)
+        next_data, reward, done, info = env.step(action)
+        next_data.update(u_ref=env.u_ref(next_data))
+        self.algo.post_step(data, action, reward, done, next_data)
+        self.data = env.reset() if done else next_data
 
     def flush(self):
         pass
@@ -85,6 +119,11 @@ def main():
     p.add_argument("--rollout-steps", type=int, default=1024)
     p.add_argument("--train-steps", type=int, default=1024)
     p.add_argument("--batch-size", type=int, default=512)
+    p.add_argument("--algo", type=str, default="gcbf",
+                   choices=["gcbf", "macbf"])
+    p.add_argument("--max-neighbors", type=int, default=None)
+    p.add_argument("--eager", action="store_true",
+                   help="also measure the plain single-scene loop")
     args = p.parse_args()
     assert all(args.batch_size % b == 0 for b in args.envs)
 
@@ -92,22 +131,28 @@ def main():
     dev = torch.device("cuda")
     params = make_env(args.env, args.num_agents, dev).default_params
     params["num_obs"] = args.obs
-    env = make_env(args.env, args.num_agents, dev, params=params)
+    capped = args.algo == "macbf" or args.max_neighbors is not None
+    env = make_env(args.env, args.num_agents, dev, params=params,
+                   max_neighbors=args.max_neighbors)
     env.train()
-    algo = make_algo("gcbf", env, args.num_agents, env.node_dim,
+    algo = make_algo(args.algo, env, args.num_agents, env.node_dim,
                      env.edge_dim, env.action_dim, dev,
                      batch_size=args.batch_size)
     enable_bf16(algo)
     env.reset()
 
-    engines = {"single": _Single(env, algo)}
+    engines = {"single": _Single(env, algo, capped)}
     for b in args.envs:
-        engines[f"vec{b}"] = VecRolloutEngine(env, algo, b)
+        engines[f"vec{b}"] = VecRolloutEngine(env, algo, b, capped=capped)
+    if args.eager:
+        engines["eager"] = _Eager(env, algo)
     # warmup: every engine, and one update (builds the ring batches' plans)
     for eng in engines.values():
         _collect(eng, 256)
         eng.flush()
-    algo.update(args.batch_size, None)
+    if args.train_steps > 0:
+        algo.update(args.batch_size, None)
+    algo.buffer.clear()
 
     res = {k: {"rollout": [], "training": []} for k in engines}
     for _ in range(args.rounds):
@@ -116,13 +161,18 @@ def main():
                 rollout_rate(eng, args.rollout_steps))
             eng.flush()
             algo.buffer.clear()
+        if args.train_steps <= 0:
+            continue
         for name, eng in engines.items():
             res[name]["training"].append(
                 training_rate(eng, algo, args.train_steps, args.batch_size))
 
-    print(f"# {args.env} n={args.num_agents} obs={args.obs}, "
+    print(f"# {args.env} n={args.num_agents} obs={args.obs} "
+          f"algo={args.algo} max_neighbors={args.max_neighbors}, "
           f"{args.rounds} alternated rounds, env-steps/s min..max")
     for metric in ("rollout", "training"):
+        if not res["single"][metric]:
+            continue
         base = res["single"][metric]
         for name in engines:
             v = res[name][metric]
@@ -138,7 +188,9 @@ def main():
             print(f"{metric:9s} {name:7s} {min(v):10.1f} .. {max(v):10.1f}"
                   f"{verdict}")
     print(json.dumps({"env": args.env, "n": args.num_agents,
-                      "obs": args.obs, "batch_size": args.batch_size,
+                      "obs": args.obs, "algo": args.algo,
+                      "max_neighbors": args.max_neighbors,
+                      "batch_size": args.batch_size,
                       "results": res}))
 
 

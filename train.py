@@ -149,12 +149,15 @@ if __name__ == "__main__":
     parser.add_argument("--num-envs", type=int, default=1,
                         help="collect from this many independent scenes per "
                              "captured rollout step (--batch-size must be a "
-                             "multiple of it; 1: the single-scene engine)")
+                             "multiple of it; 1: the single-scene engine). "
+                             "MACBF and neighbour-capped scenes take this "
+                             "path only together with --capture-capped")
     parser.add_argument("--capture-capped", action="store_true",
                         default=os.environ.get(
                             "GCBF_AMD_CAPTURE_CAPPED", "0") == "1",
                         help="collect MACBF / neighbour-capped rollouts with "
                              "the captured engine too (also "
                              "GCBF_AMD_CAPTURE_CAPPED=1; default: their "
-                             "eager loop)")
+                             "eager loop); with --num-envs B that engine is "
+                             "the vectorized one, B scenes per step")
     train(parser.parse_args())
